@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput bench of the 2D-3D matching forward on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]          (N > 1: spawns one rank per GPU itself)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]     (N > 1: spawns one rank per GPU itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -143,7 +143,14 @@ def parse_args():
                     help="B=1 forwards kept in flight per GPU on separate HIP streams (the reference runs "
                          "2 Ray workers per GPU, inference_OnePosePlus.py:18-26); measured with the throughput tiles (r05, one box): "
                          "2 / 3 / 4 / 5 streams = 493 / 523 / 530 / 530 images/s")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the forwards of the last timed step returned as DIR/<name>.npy (float32 / float64; "
+                         "matrices above %d elements as a fixed seeded sample) so that two builds can be compared output for output"
+                         % DUMP_FULL_MAX)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def main():
@@ -354,14 +361,18 @@ def run(args):
                     (mods or models)[slot](d)
         return d
 
-    def run_steps(n, pool=None, mods=None):
+    def run_steps(n, pool=None, mods=None, keep=None):
         """EXACTLY n forwards (callers pass steps x images_per_step).  With several streams one host thread per stream keeps its forward in flight (the
         forward's single D2H sync of the match count releases the GIL); the threads draw step indices from one
-        shared counter, so no stream idles while another still has a backlog."""
+        shared counter, so no stream idles while another still has a backlog.  keep (a dict): filled with forward index -> returned dict for
+        the forwards of the last step (references only, no device work)."""
+        first_kept = n - ips
         if n_streams == 1:
             last = None
             for i in range(n):
                 last = step(i, 0, pool, mods)
+                if keep is not None and i >= first_kept:
+                    keep[i] = last
             return last
         out = [None] * n_streams
         nxt = [0]
@@ -376,6 +387,8 @@ def run(args):
                 if i >= n:
                     break
                 out[slot] = step(i, slot, pool, mods)
+                if keep is not None and i >= first_kept:
+                    keep[i] = out[slot]
             streams[slot].synchronize()
         th = [threading.Thread(target=worker, args=(k,)) for k in range(n_streams)]
         for t in th:
@@ -398,8 +411,12 @@ def run(args):
     lib = _lib.load()
     prof = (not args.no_roofline) and rank == 0 and world == 1
 
-    last, own_elapsed, elapsed = timed_region(run_steps, args.steps * ips, barrier, lambda: torch.cuda.synchronize(dev))
+    kept = {} if args.dump_outputs else None
+    last, own_elapsed, elapsed = timed_region(lambda n: run_steps(n, keep=kept), args.steps * ips, barrier, lambda: torch.cuda.synchronize(dev))
     matches_last = int(last["mconf"].numel())
+    if kept is not None:
+        dump_outputs(args.dump_outputs, kept, datas[0].keys(), args.steps * ips - ips, "rank%d_" % rank if world > 1 else "")
+        kept = None
     obj = model._rt.get("obj")       # (key, tokens, sources, event, transformer-prefix blob or None) as the timed region left it
     cache_on = bool(getattr(model, "cache_object_tokens", True)) and obj is not None and obj[4] is not None
     props = torch.cuda.get_device_properties(dev)
@@ -514,6 +531,45 @@ def write_detail(detail):
         except OSError:
             pass
     return where
+
+
+DUMP_FULL_MAX = 1 << 20      # --dump-outputs: arrays up to this many elements are written whole, larger ones as a sample
+DUMP_SAMPLE = 1 << 18        # elements of that sample: fixed positions drawn from a seeded generator, the same for every run and build
+DUMP_LIMIT = 64 << 20        # bytes written by --dump-outputs in all
+
+
+def dump_outputs(out_dir, kept, input_keys, first, prefix=""):
+    """--dump-outputs: the arrays the forwards of the last timed step returned (every tensor the forward added to its dict, not the
+    inputs; empty ones -- the match lists when a forward finds no match -- are left out) -> out_dir/<prefix>fKK_<name>.npy, KK = the
+    forward's position in the step.  Floating tensors as float32 (float64 stays
+    float64), integer / bool tensors as float64 (exact: the indices are far below 2^53).  An array of more than DUMP_FULL_MAX elements
+    (the N x L confidence matrix) is written as `<name>_sample` at the flat positions stored in <prefix>sample_index_n<numel>.npy."""
+    import numpy as np
+    import torch
+    files, index = {}, {}
+    for i in sorted(kept):
+        for name, t in sorted(kept[i].items()):
+            if name in input_keys or not torch.is_tensor(t) or t.numel() == 0:
+                continue
+            wide = t.dtype == torch.float64 or not t.is_floating_point()
+            a = (t.double() if wide else t.float()).detach().cpu().reshape(-1).numpy()
+            if a.size > DUMP_FULL_MAX:
+                if a.size not in index:
+                    pos = np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False)
+                    index[a.size] = np.sort(pos)
+                    files["%ssample_index_n%d" % (prefix, a.size)] = index[a.size].astype(np.float64)
+                a, name = a[index[a.size]], name + "_sample"
+            else:
+                a = a.reshape(tuple(t.shape))
+            files["%sf%02d_%s" % (prefix, i - first, name)] = a
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes for %d forwards exceed the %d-byte limit (lower --images-per-step)"
+                         % (total, len(kept), DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    sys.stderr.write("--dump-outputs: %d arrays, %.1f MB -> %s\n" % (len(files), total / 2**20, out_dir))
 
 
 def bounded_dumps(obj, limit=LINE_LIMIT):

@@ -42,6 +42,13 @@ def _hipcc():
     return "hipcc"
 
 
+def _max_jobs():
+    """parallel hipcc processes: MAX_JOBS when set, else the CPUs this process may run on (not every CPU of the machine)"""
+    if os.environ.get("MAX_JOBS", "").isdigit() and int(os.environ["MAX_JOBS"]) > 0:
+        return int(os.environ["MAX_JOBS"])
+    return len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 4)
+
+
 def source_hash():
     """sha256 over the names and contents of every source / header of the library (None if the sources are not there)"""
     h = hashlib.sha256()
@@ -109,7 +116,7 @@ def _build(force, verbose, OBJ, LIB, FLAGS, SOURCE_FLAGS):
         return job, r
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), _max_jobs())) as ex:
             for (s, o, _), r in ex.map(compile_one, jobs):
                 if verbose and r.stderr.strip():
                     sys.stderr.write(r.stderr)

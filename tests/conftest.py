@@ -10,6 +10,9 @@ if ROOT not in sys.path:
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
+    import torch
+    from tests.golden.cases import GOLDEN_CPU_THREADS
+    torch.set_num_threads(GOLDEN_CPU_THREADS)       # CPU results compared with tests/golden/ are reproduced at the thread count of their generation
 
 
 @pytest.fixture(scope="session")

@@ -2,6 +2,11 @@
 only) and the tests (oracle side / HIP side).  Inputs are regenerated from seeds
 (onepose_plus_plus_amd/synthetic.py); only reference OUTPUTS are stored in the .npz files."""
 
+# torch CPU threads of the golden runs AND of the tests that compare against them: the split of a CPU convolution across threads
+# changes with the thread count (from about 12 threads up the 1/2-resolution backbone map moves by ~2e-5), so the oracle side runs
+# with the thread count the vectors were produced with, whatever the machine has
+GOLDEN_CPU_THREADS = 8
+
 # end-to-end forward cases: name -> (hw, n_points, thr, weight_seed, input_seed, fine_enabled)
 E2E_CASES = {
     "e2e_128x128_n300_thr0": ((128, 128), 300, 0.0, 0, 1, True),
@@ -93,3 +98,21 @@ def make_assign_inputs(case):
     am[:, k // 2: k // 2 + k // 20] = am[:, : k // 20]                                            # repeated pairs
     am[1, k - k // 25:] = am[1, k - 2 * (k // 25): k - k // 25]                                    # same 3D point from other keypoints
     return kc, kf, am, {"shape3d": N, "L": hc * wc, "w_c": wc, "scale": sc, "coarse_scale": 1.0 / 8}
+
+
+# the object-bank reader on .npz files in the reference's anno_3d_average layout: name -> (n_points, shape3d); above shape3d the
+# reader draws a with-replacement sub-sample from the torch RNG, seeded with ANNO3D_TORCH_SEED right before the read
+ANNO3D_CASES = {
+    "anno3d_n300_s7000": (300, 7000),
+    "anno3d_n900_s500": (900, 500),
+}
+ANNO3D_TORCH_SEED = 77
+
+
+def write_anno3d_case(path, n):
+    """the seeded .npz that both the reference's read_anno3d and ObjectBank.from_npz read"""
+    import numpy as np
+    from onepose_plus_plus_amd.bank import ObjectBank
+    rng = np.random.default_rng(n)
+    ObjectBank.save_npz(path, rng.standard_normal((n, 3)), rng.standard_normal((128, n)).astype(np.float32),
+                        np.ones((n, 1)), rng.standard_normal((256, n)).astype(np.float32))

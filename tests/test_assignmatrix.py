@@ -30,23 +30,6 @@ def test_oracle_matches_reference_fixture(name):
     assert int((a[1] >= meta["shape3d"]).sum()) > 0 and int(conf.sum()) < int((a[1] < meta["shape3d"]).sum())
 
 
-def test_reference_method_live():
-    """when /root/reference is mounted: the reference's own method (compiled from its source) reproduces the committed fixtures"""
-    import os
-    if not os.path.isdir("/root/reference/src/datasets"):
-        pytest.skip("reference tree not mounted")
-    import types
-    from tests.golden.gen_assignmatrix_golden import reference_method
-    fn = reference_method()
-    for name, case in ASSIGN_CASES.items():
-        kc, kf, am, meta = make_assign_inputs(case)
-        self = types.SimpleNamespace(shape3d=meta["shape3d"], n_query_coarse_grid=meta["L"], w_c=meta["w_c"], query_img_scale=meta["scale"],
-                                     coarse_scale=meta["coarse_scale"])
-        conf, floc = fn(self, kc, kf, am)
-        gconf, gfloc = _dense_from_golden(H.load_golden(name))
-        assert torch.equal(conf, gconf) and torch.equal(floc, gfloc), name
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", list(ASSIGN_CASES))
 def test_hip_builder_matches_reference_fixture(name):

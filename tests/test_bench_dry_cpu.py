@@ -93,3 +93,33 @@ def test_executed_flops_exclude_the_cached_object_prefix():
     assert round(bench.flops_per_image(5000, False) / 1e9, 1) == 337.3
     assert round(bench.flops_per_image(5000, True) / 1e9, 1) == 328.5
     assert round(bench.flops_per_image(2000, False) / 1e9, 1) == 306.8 and round(bench.flops_per_image(15000, False) / 1e9, 1) == 438.8
+
+
+def test_dump_outputs_writes_the_returned_arrays(tmp_path):
+    """--dump-outputs: every non-empty tensor the forward added (not the inputs), float32 / float64 only, the large matrix as a fixed
+    sample that is the same from run to run, names keyed by the forward's position in the last step."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    inputs = {"query_image": torch.rand(1, 1, 8, 8)}
+
+    def fwd(seed):
+        g = torch.Generator().manual_seed(seed)
+        return dict(inputs, conf_matrix=torch.rand(1, 2000, 1024, generator=g), i_ids=torch.arange(7), mconf=torch.rand(7, generator=g),
+                    gt_mask=torch.zeros(7, dtype=torch.bool), j_ids=torch.zeros(0, dtype=torch.int64), bs=1)
+    kept = {30: fwd(1), 31: fwd(2)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), kept, inputs.keys(), 30)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == sorted(
+        ["f%02d_%s.npy" % (k, n) for k in (0, 1) for n in ("conf_matrix_sample", "i_ids", "mconf", "gt_mask")] + ["sample_index_n2048000.npy"])
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.array_equal(a, b), n
+    idx = np.load(tmp_path / "a" / "sample_index_n2048000.npy").astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE and len(np.unique(idx)) == len(idx)
+    assert np.array_equal(np.load(tmp_path / "a" / "f01_conf_matrix_sample.npy"), kept[31]["conf_matrix"].reshape(-1).numpy()[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "f00_i_ids.npy"), np.arange(7, dtype=np.float64))
+    assert np.load(tmp_path / "a" / "f00_mconf.npy").dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= bench.DUMP_LIMIT
