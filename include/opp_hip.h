@@ -85,6 +85,14 @@ typedef struct opp_config {
    * of the coarse level and the chip-filling convolutions of the fine branch share the device.  Results are identical (same
    * kernels, same order within each branch); the workspace holds both branches' buffers at once.  0 = one stream. */
   int fpn_overlap;
+  /* loftr_coarse.attention / loftr_fine.attention (transformer.py:32-40): 0 = "linear" (LinearAttention, elu + 1 feature map; the default,
+   * what a zero-initialised config selects), 1 = any other value upstream = FullAttention, softmax(Q K^T / sqrt(D)) V
+   * (linear_attention.py:64-95; csrc/full_attention.hip).  With full attention at a level every layer there runs the plain Q/K/V projection,
+   * opp_full_attention's kernels and the unchanged merge / norm / MLP tail; the per-object prefix is off when the coarse level is full
+   * (opp_object_prefix_bytes = 0) and a query mask is refused (upstream cannot run a masked forward with a cross layer either).
+   * opp_create refuses other values (OPP_ERR_UNSUPPORTED). */
+  int coarse_attention;
+  int fine_attention;
 } opp_config;
 
 typedef struct opp_ctx opp_ctx;
@@ -439,6 +447,16 @@ int opp_conv_packed_k(int cin, int ks);
 size_t opp_linear_attention_workspace_bytes(int n_seg, int len0, int len1, int C, int nhead);
 int opp_linear_attention(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross,
                          float* msg, void* workspace, size_t workspace_bytes, void* stream);
+/* FullAttention (loftr_module/linear_attention.py:64-95, selected by transformer.py:32-40 for any `attention` but "linear") of the
+ * two token streams of one encoder layer, same row layout as opp_linear_attention but qkv holds the PLAIN projections Q | K | V.
+ * Per head (D = C / nhead): msg = softmax(Q K^T / sqrt(D)) V over the source tokens of the same segment (cross = 0: the row's own
+ * stream, 1: the other stream); no mask, no dropout.  precision = opp_config.gemm_precision: 0 fp32 MFMA, 3 bf16x3 (six bf16 MFMAs per
+ * product, not narrower than fp32); other values return OPP_ERR_UNSUPPORTED.  D = 32 with a stream longer than 32 rows runs the flash
+ * kernel (online softmax, K / V tiles through LDS), everything else (the fine level: 25 + 1 tokens, D = 16) an exact-fp32 vector-ALU
+ * kernel.  Supported: len0, len1 >= 1, C % nhead == 0, D in {16, 32}.  Needs no workspace (the size query returns 0; ws may be NULL). */
+size_t opp_full_attention_workspace_bytes(int n_seg, int len0, int len1, int C, int nhead);
+int opp_full_attention(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross, int precision,
+                       float* msg, void* workspace, size_t workspace_bytes, void* stream);
 /* The tile configuration the GEMM / implicit-GEMM convolution launcher picks by itself (tile_cfg < 0) for an M x n_store output over K (a multiple
  * of 32) -- a pure host function of shape, operand arithmetic (prec as in opp_conv2d_nhwc) and tile policy (0 latency, 1 throughput: opp_config.tile_policy),
  * exported so that the policy is testable without a device.  n_real = real output channels when n_store is their padded count (0 = unknown), conv != 0

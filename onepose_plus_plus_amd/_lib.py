@@ -37,6 +37,8 @@ class OppConfig(Structure):
         ("encoder_fusion", c_int),
         ("score_two_sweep", c_int),
         ("fpn_overlap", c_int),
+        ("coarse_attention", c_int),
+        ("fine_attention", c_int),
     ]
 
 
@@ -123,6 +125,8 @@ SIGNATURES = {
     "opp_linear_attention_train_backward": (c_int, [c_void_p] * 8 + [c_int] * 5 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "opp_linear_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "opp_linear_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "opp_full_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "opp_full_attention": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_pack_conv_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "opp_gemm_tile_for": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "opp_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -20,19 +20,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_build")
 LIB = os.path.join(HERE, "libopp_hip.so")
-SOURCES = ["gemm_mfma.hip", "gemm_ss.hip", "enc_chain.hip", "enc_layer64.hip", "stem_direct.hip", "attention.hip", "backbone.hip", "kpt.hip",
+SOURCES = ["gemm_mfma.hip", "gemm_ss.hip", "enc_chain.hip", "enc_layer64.hip", "stem_direct.hip", "attention.hip", "full_attention.hip", "backbone.hip", "kpt.hip",
            "coarse_match.hip", "fine.hip", "pnp.hip", "ingest.hip", "profile.hip", "bn_train.hip", "bankbuild.hip", "loss.hip", "linear_bwd.hip",
            "linattn_train.hip", "conv_bwd.hip", "train_misc.hip", "conv_tail.hip", "version.hip", "api.hip"]
 HEADERS = ["opp_common.h", "opp_internal.h", "enc_frag.h", "pnp_math.h", os.path.join("..", "..", "include", "opp_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
-# per-source extras.  The two files whose kernels split fp32 values into bf16 triples beside MFMAs: the SLP vectorizer pairs the
+# per-source extras.  The files whose kernels split fp32 values into bf16 triples beside MFMAs: the SLP vectorizer pairs the
 # residual subtractions of the split into v_pk_add_f32, which costs more there than the two scalar adds it replaces
 # (MI355X_MICROARCH.md, "price of one filler beside MFMAs"; +0.4 % images/s, profiles/r04_ab_slp_vectorizer.txt).  The scalar and
 # the packed forms contract into FMAs differently, so arithmetic that two files must round identically (the LayerNorm of the fused
 # encoder chain against the launch-per-Linear path) is written with explicit FMAs (opp_common.h: opp_ln_*), not left to the flags.
 # (Every source without the vectorizer, `--variant noslp_all`: +0.2 % at most and the coarse-level chain loses its bit-identity through the
 # attention arithmetic -- profiles/r04_ab_slp_all_sources.txt -- so the other files keep it.)
-SOURCE_FLAGS = {"conv_bwd.hip": ["-fno-slp-vectorize"], "gemm_mfma.hip": ["-fno-slp-vectorize"]}
+SOURCE_FLAGS = {"conv_bwd.hip": ["-fno-slp-vectorize"], "gemm_mfma.hip": ["-fno-slp-vectorize"], "full_attention.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():

@@ -254,6 +254,14 @@ extern "C" int opp_create(const opp_config* cfg, opp_ctx** out) {
   OPP_CHECK_ARG(cfg->fpn_overlap == 0 || cfg->fpn_overlap == 1, "fpn_overlap must be 0 or 1");
   OPP_CHECK_ARG(cfg->score_two_sweep >= 0 && cfg->score_two_sweep <= 2, "score_two_sweep must be 0, 1 or 2");
   OPP_CHECK_ARG(cfg->fine_window >= 1 && cfg->fine_window * cfg->fine_window <= 64 && (cfg->fine_window & 1), "bad fine window");
+  if ((cfg->coarse_attention != 0 && cfg->coarse_attention != 1) || (cfg->fine_attention != 0 && cfg->fine_attention != 1)) {
+    opp_set_error("coarse_attention / fine_attention must be 0 (linear) or 1 (full), got %d / %d", cfg->coarse_attention, cfg->fine_attention);
+    return OPP_ERR_UNSUPPORTED;
+  }
+  if ((cfg->coarse_attention || cfg->fine_attention) && cfg->gemm_precision != 0 && cfg->gemm_precision != 3) {
+    opp_set_error("full attention runs in gemm_precision 0 (fp32) or 3 (bf16x3), got %d", cfg->gemm_precision);
+    return OPP_ERR_UNSUPPORTED;
+  }
   opp_ctx* c = new opp_ctx();
   c->cfg = *cfg;
   const int d0 = cfg->initial_dim, d1 = cfg->block_dims[0], d2 = cfg->block_dims[1], d3 = cfg->block_dims[2];
@@ -1577,11 +1585,106 @@ ObjPrefix obj_prefix_view(float* base, int C, int D, int n) {
   return p;
 }
 // the fused default path only (bf16x3, one 64-token layer kernel per layer): every other configuration computes the whole layer
+// (linear coarse attention only: with full attention the layer-1 apply of the image stream needs the 3D stream's K / V rows themselves)
 bool obj_prefix_ok(const opp_ctx* c) {
-  return c->cfg.gemm_precision == 3 && c->cfg.encoder_fusion == 2 && c->cfg.coarse_n_layers >= 2 && c->cfg.coarse_is_cross[0] == 0 &&
+  return c->cfg.coarse_attention == 0 && c->cfg.gemm_precision == 3 && c->cfg.encoder_fusion == 2 && c->cfg.coarse_n_layers >= 2 && c->cfg.coarse_is_cross[0] == 0 &&
          c->cfg.coarse_is_cross[1] == 1 && c->cfg.coarse_d_model == 256 && c->cfg.coarse_nhead == 8 && c->tr_packed;
 }
 enum { OPP_PREFIX_NONE = 0, OPP_PREFIX_USE = 1, OPP_PREFIX_MAKE = 2 };
+
+// merge -> norm1 -> mlp.0 -> ReLU -> mlp.2 -> norm2 -> +x of one LoFTREncoderLayer (transformer.py:86-94) as dense GEMMs + LayerNorms on
+// the message b.msg of all T rows, in place on X
+int encoder_tail_dense(const EncLayerDesc& e, float* X, const TrBufs& b, int T, int C, bool fuse_ln, float eps_ln, hipStream_t s, int h2) {
+  if (fuse_ln) {
+    // merge -> norm1 and mlp.2 -> norm2 -> +x in the GEMM epilogues (64-row tiles spanning the whole row)
+    LnArgs n1, n2;
+    n1.gamma = e.g1;
+    n1.beta = e.b1;
+    n1.eps = eps_ln;
+    n2.gamma = e.g2;
+    n2.beta = e.b2;
+    n2.res = X;
+    n2.ldres = C;
+    n2.eps = eps_ln;
+    OPP_TRY(dense_gemm(b.msg, C, nullptr, 0, C, e.wmerge, T, C, C, b.mrg, OPP_ACT_NONE, s, h2, e.smerge, &n1));   // merge + norm1 (:86-87)
+    OPP_TRY(dense_gemm(X, C, b.mrg, C, C, e.w1, T, 2 * C, 2 * C, b.hid, OPP_ACT_RELU, s, h2, e.s1));               // mlp.0 on cat([x,msg]) (:91)
+    return dense_gemm(b.hid, 2 * C, nullptr, 0, 2 * C, e.w2, T, C, 2 * C, X, OPP_ACT_NONE, s, h2, e.s2, &n2);      // mlp.2 + norm2 + x (:92-94)
+  }
+  OPP_TRY(dense_gemm(b.msg, C, nullptr, 0, C, e.wmerge, T, C, C, b.mrg, OPP_ACT_NONE, s, h2, e.smerge));  // merge (:86)
+  OPP_TRY(opp_layernorm(b.mrg, C, e.g1, e.b1, nullptr, 0, b.msg, C, T, C, eps_ln, s));              // norm1 (:87)
+  OPP_TRY(dense_gemm(X, C, b.msg, C, C, e.w1, T, 2 * C, 2 * C, b.hid, OPP_ACT_RELU, s, h2, e.s1));  // mlp.0 on cat([x,msg]) (:91)
+  OPP_TRY(dense_gemm(b.hid, 2 * C, nullptr, 0, 2 * C, e.w2, T, C, 2 * C, b.mrg, OPP_ACT_NONE, s, h2, e.s2));  // mlp.2
+  return opp_layernorm(b.mrg, C, e.g2, e.b2, X, C, X, C, T, C, eps_ln, s);                          // x + norm2 (:92-94)
+}
+
+// LocalFeatureTransformer.forward with FullAttention layers (transformer.py:32-40: `attention` != "linear"): per layer the plain q / k / v
+// projections of both streams in one GEMM (transformer.py:76-78, no feature map, no V / S), softmax attention into b.msg
+// (csrc/full_attention.hip), then the unchanged merge / norm1 / MLP / norm2 / residual tail -- one fused launch per layer where the linear
+// path has one behind a given message (opp_enc_chain, apply = 0), the dense GEMMs otherwise.  None of the kernels that apply LINEAR attention
+// inside the layer (fold path, chain apply, opp_enc_layer64) runs here.
+int transformer_full_impl(const std::vector<EncLayerDesc>& layers, const int* is_cross, int C, int nhead, float* X, int n_seg, int len0,
+                          int len1, Arena& a, hipStream_t s, int h2, int fusion) {
+  const int D = C / nhead;
+  const int T = n_seg * (len0 + len1);
+  if (T == 0 || layers.empty()) return OPP_OK;
+  OPP_CHECK_ARG(h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3, "transformer: full attention runs in fp32 or bf16x3");
+  OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: full attention needs both token streams");
+  TrBufs b;
+  plan_transformer(C, D, n_seg, len0, len1, a, b);
+  if (!a.ok) {
+    opp_set_error("transformer: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
+  const float eps_ln = 1e-5f;
+  static const int fuse_env = getenv("OPP_FUSE_LN") ? atoi(getenv("OPP_FUSE_LN")) : 1;   // tuning knob
+  const bool fuse_ln = fuse_env && (C == 256 || C == 128);
+  for (size_t li = 0; li < layers.size(); ++li) {
+    const EncLayerDesc& e = layers[li];
+    OppGemm g;
+    g.nonfinite = t_status_flag;
+    g.tile_policy = t_tile_policy;
+    g.A0 = X;
+    g.lda0 = C;
+    g.ksplit = C;
+    g.W = e.wqkv;
+    g.ldw = (int)split_floats((size_t)C, h2);
+    g.M = T;
+    g.N = 3 * C;
+    g.K = C;
+    g.C = b.qkv;
+    g.ldc = 3 * C;
+    g.n_store = 3 * C;
+    g.act = OPP_ACT_NONE;
+    g.prec = h2;
+    OPP_TRY(opp_gemm_launch(g, s));
+    OPP_TRY(opp_full_attention_run(b.qkv, n_seg, len0, len1, C, nhead, is_cross[li] != 0, h2, b.msg, s));
+    if (fusion && h2 == OPP_PREC_BF16X3 && e.fmerge && opp_enc_chain_ok(C, nhead, false)) {
+      OppEncChain ch;
+      ch.C = C;
+      ch.X = X;
+      ch.ldx = C;
+      ch.out = X;
+      ch.ldo = C;
+      ch.len0 = T;
+      ch.len1 = 0;
+      ch.msg = b.msg;
+      ch.ldm = C;
+      ch.apply = 0;
+      ch.wm = e.fmerge;
+      ch.w1 = e.f1;
+      ch.w2 = e.f2;
+      ch.g1 = e.g1;
+      ch.b1 = e.b1;
+      ch.g2 = e.g2;
+      ch.b2 = e.b2;
+      ch.eps_ln = eps_ln;
+      OPP_TRY(opp_enc_chain(ch, s));
+      continue;
+    }
+    OPP_TRY(encoder_tail_dense(e, X, b, T, C, fuse_ln, eps_ln, s, h2));
+  }
+  return OPP_OK;
+}
 
 // LocalFeatureTransformer.forward (transformer.py:133-171) on X = [stream0 ; stream1]
 // prefix_mode OPP_PREFIX_USE: X's stream-1 rows already hold ObjPrefix::x1; layer 0 then runs on stream 0 only and layer 1 projects /
@@ -1692,27 +1795,7 @@ int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cros
       continue;
     }
     OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, len1, cross, b.kv, b.ks, b.scratch, b.msg, eps_attn, s));
-    if (fuse_ln) {
-      // merge -> norm1 and mlp.2 -> norm2 -> +x in the GEMM epilogues (64-row tiles spanning the whole row)
-      LnArgs n1, n2;
-      n1.gamma = e.g1;
-      n1.beta = e.b1;
-      n1.eps = eps_ln;
-      n2.gamma = e.g2;
-      n2.beta = e.b2;
-      n2.res = X;
-      n2.ldres = C;
-      n2.eps = eps_ln;
-      OPP_TRY(dense_gemm(b.msg, C, nullptr, 0, C, e.wmerge, T, C, C, b.mrg, OPP_ACT_NONE, s, h2, e.smerge, &n1));   // merge + norm1 (:86-87)
-      OPP_TRY(dense_gemm(X, C, b.mrg, C, C, e.w1, T, 2 * C, 2 * C, b.hid, OPP_ACT_RELU, s, h2, e.s1));               // mlp.0 on cat([x,msg]) (:91)
-      OPP_TRY(dense_gemm(b.hid, 2 * C, nullptr, 0, 2 * C, e.w2, T, C, 2 * C, X, OPP_ACT_NONE, s, h2, e.s2, &n2));    // mlp.2 + norm2 + x (:92-94)
-    } else {
-    OPP_TRY(dense_gemm(b.msg, C, nullptr, 0, C, e.wmerge, T, C, C, b.mrg, OPP_ACT_NONE, s, h2, e.smerge));  // merge (:86)
-    OPP_TRY(opp_layernorm(b.mrg, C, e.g1, e.b1, nullptr, 0, b.msg, C, T, C, eps_ln, s));              // norm1 (:87)
-    OPP_TRY(dense_gemm(X, C, b.msg, C, C, e.w1, T, 2 * C, 2 * C, b.hid, OPP_ACT_RELU, s, h2, e.s1));  // mlp.0 on cat([x,msg]) (:91)
-    OPP_TRY(dense_gemm(b.hid, 2 * C, nullptr, 0, 2 * C, e.w2, T, C, 2 * C, b.mrg, OPP_ACT_NONE, s, h2, e.s2));  // mlp.2
-    OPP_TRY(opp_layernorm(b.mrg, C, e.g2, e.b2, X, C, X, C, T, C, eps_ln, s));                        // x + norm2 (:92-94)
-    }
+    OPP_TRY(encoder_tail_dense(e, X, b, T, C, fuse_ln, eps_ln, s, h2));
   }
   return OPP_OK;
 }
@@ -1801,6 +1884,22 @@ extern "C" int opp_linear_attention(const float* qkv, int n_seg, int len0, int l
   return run_linattn(qkv, C, C / nhead, n_seg, len0, len1, cross != 0, kv, ks, sc, msg, 1e-6f, (hipStream_t)stream);
 }
 
+extern "C" size_t opp_full_attention_workspace_bytes(int n_seg, int len0, int len1, int C, int nhead) {
+  (void)n_seg, (void)len0, (void)len1, (void)C, (void)nhead;
+  return 0;   // no split-KV: the kernels need no scratch
+}
+
+extern "C" int opp_full_attention(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross, int precision, float* msg,
+                                  void* ws, size_t ws_bytes, void* stream) {
+  (void)ws, (void)ws_bytes;
+  if (precision != 0 && precision != 3) {
+    opp_set_error("full_attention: precision must be 0 (fp32) or 3 (bf16x3), got %d", precision);
+    return OPP_ERR_UNSUPPORTED;
+  }
+  return opp_full_attention_run(qkv, n_seg, len0, len1, C, nhead, cross != 0, precision == 3 ? OPP_PREC_BF16X3 : OPP_PREC_FP32, msg,
+                                (hipStream_t)stream);
+}
+
 extern "C" size_t opp_transformer_workspace_bytes(const opp_ctx* ctx, int which, int n_seg, int len0, int len1) {
   if (!ctx) return 0;
   const int C = which == 0 ? ctx->cfg.coarse_d_model : ctx->cfg.fine_d_model;
@@ -1817,6 +1916,15 @@ extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg
   OPP_CHECK_ARG(ctx->tr_packed, "transformer: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(which == 0 || which == 1, "transformer: which must be 0 or 1");
   Arena a(ws, ws_bytes);
+  if (which == 0 && ctx->cfg.coarse_attention) {
+    OPP_CHECK_ARG(n_seg != 1 || !ctx->query_mask, "transformer: full attention with a query mask is unsupported (upstream FullAttention indexes the "
+                                                  "None q_mask of the cross layers, linear_attention.py:84-85)");
+    return transformer_full_impl(ctx->coarse, ctx->cfg.coarse_is_cross, ctx->cfg.coarse_d_model, ctx->cfg.coarse_nhead, tokens, n_seg, len0, len1, a,
+                                 (hipStream_t)stream, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion);
+  }
+  if (which == 1 && ctx->cfg.fine_attention)
+    return transformer_full_impl(ctx->fine, ctx->cfg.fine_is_cross, ctx->cfg.fine_d_model, ctx->cfg.fine_nhead, tokens, n_seg, len0, len1, a,
+                                 (hipStream_t)stream, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion);
   if (which == 0)
     return transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, ctx->cfg.coarse_d_model, ctx->cfg.coarse_nhead, tokens, n_seg, len0, len1, a, (hipStream_t)stream, gemm_prec(ctx->cfg),
                             n_seg == 1 ? ctx->query_mask : nullptr, ctx->cfg.encoder_fusion);
@@ -1965,6 +2073,8 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   OPP_CHECK_ARG(ctx->tr_packed, "forward_coarse: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(n > 0, "forward_coarse: empty point cloud");
   OPP_CHECK_ARG(!ctx->cfg.pos_enc_enable || pe, "forward_coarse: positional encoding enabled but pe is null");
+  OPP_CHECK_ARG(!ctx->cfg.coarse_attention || !ctx->query_mask, "forward_coarse: full attention with a query mask is unsupported (upstream "
+                                                                "FullAttention indexes the None q_mask of the cross layers, linear_attention.py:84-85)");
   hipStream_t s = (hipStream_t)stream;
   Arena a(ws, ws_bytes);
   float *feat_c, *tokens;
@@ -2050,8 +2160,12 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   if (use_prefix) pre = obj_prefix_view(const_cast<float*>(ctx->obj_prefix), C, C / ctx->cfg.coarse_nhead, n);
   OPP_TRY(coarse_tokens_impl(ctx, feat_c, ctx->cfg.pos_enc_enable ? pe : nullptr, L, kpts, bank_c, n, use_prefix ? pre.x1 : tokens3d_pre, tokens, a, s));
   a.off = mark;
-  OPP_TRY(transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg), ctx->query_mask,
-                           ctx->cfg.encoder_fusion, use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE, use_prefix ? &pre : nullptr));
+  if (ctx->cfg.coarse_attention)   // use_prefix is false here (obj_prefix_ok); the query mask was refused on entry
+    OPP_TRY(transformer_full_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg),
+                                  ctx->cfg.encoder_fusion));
+  else
+    OPP_TRY(transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg), ctx->query_mask,
+                             ctx->cfg.encoder_fusion, use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE, use_prefix ? &pre : nullptr));
   a.off = mark;
   return coarse_match_impl(ctx, tokens + (size_t)L * C, tokens, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c,
                            mkpts_3d, count, a, s);
@@ -2066,7 +2180,9 @@ int fine_tail(opp_ctx* ctx, float* X, int M, const float* mkpts_c, float base_sc
               float* mkpts_f, Arena& a, hipStream_t s) {
   const int C = ctx->cfg.fine_d_model, Wwin = ctx->cfg.fine_window, WW = Wwin * Wwin;
   float* f3 = X + (size_t)M * WW * C;
-  if (run_transformer)
+  if (run_transformer && ctx->cfg.fine_attention)
+    OPP_TRY(transformer_full_impl(ctx->fine, ctx->cfg.fine_is_cross, C, ctx->cfg.fine_nhead, X, M, WW, 1, a, s, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion));
+  else if (run_transformer)
     OPP_TRY(transformer_impl(ctx->fine, ctx->cfg.fine_is_cross, C, ctx->cfg.fine_nhead, X, M, WW, 1, a, s, gemm_prec(ctx->cfg), nullptr, ctx->cfg.encoder_fusion));
   const float temp = (float)(1.0 / sqrt((double)C));   // fine_matching.py:82
   return opp_fine_head(f3, C, X, C, M, Wwin, C, temp, mkpts_c, base_scale, qscale, expec_f, mkpts_f, s);

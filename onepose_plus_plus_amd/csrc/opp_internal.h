@@ -66,6 +66,10 @@ int opp_dual_softmax_bwd(const float* g, const float* sim, const float* lse_row,
 // many short segment pairs (fine level: 25 window tokens + 1 point token per match): KV, Ksum and the apply of both
 // streams of one segment in one workgroup
 bool opp_linattn_small_ok(int len0, int len1, int C, int D);
+// full_attention.hip -- FullAttention (softmax(Q K^T / sqrt(D)) V, linear_attention.py:64-95) of both streams of one encoder layer:
+// qkv [n_seg * (len0 + len1)][3 C] = plain Q | K | V, msg [same rows][C]; prec OPP_PREC_FP32 or OPP_PREC_BF16X3; D = C / nhead in {16, 32}
+int opp_full_attention_run(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross, int prec, float* msg,
+                           hipStream_t stream);
 int opp_linattn_small_pair(const float* qkv, int ld, int n_seg, int len0, int len1, int cross, float* out, int ldo, int C, int D,
                            float eps, hipStream_t stream);
 int opp_linattn_apply_pair(const float* qkv, int ld, const float* kv, const float* ks, int cross, float* out, int ldo,

@@ -118,9 +118,9 @@ def _validate_config(cfg):
             raise ValueError()
         if t["norm_method"] != "layernorm":
             raise NotImplementedError("HIP path implements norm_method 'layernorm' only")
-        if t["attention"] != "linear":
-            raise NotImplementedError("HIP path implements linear attention only (FullAttention unused upstream)")
-        if t["kernel_fn"] != "elu + 1":                # linear_attention.py:14-18
+        # any value other than "linear" builds FullAttention (transformer.py:32-40); build_feature_map -- and with it the
+        # kernel_fn check (linear_attention.py:14-18) -- is only reached by LinearAttention
+        if t["attention"] == "linear" and t["kernel_fn"] != "elu + 1":
             raise ValueError()
         if t["rezero"] is not None:
             raise NotImplementedError("rezero is not supported")
@@ -362,7 +362,29 @@ class OnePosePlus_model(nn.Module):
         c.encoder_fusion = int(getattr(self, "encoder_fusion", 2))
         c.score_two_sweep = int(getattr(self, "score_two_sweep", 2))
         c.fpn_overlap = 1 if getattr(self, "fpn_overlap", True) else 0
+        c.coarse_attention = 0 if cfg["loftr_coarse"]["attention"] == "linear" else 1
+        c.fine_attention = 0 if cfg["loftr_fine"]["attention"] == "linear" else 1
         return c
+
+    def _full_attention_levels(self):
+        return [n for n in ("loftr_coarse", "loftr_fine") if self.config[n]["attention"] != "linear"]
+
+    def _check_full_attention(self, masked):
+        """Refusals of the full-attention configurations, raised before anything is launched.  Upstream FullAttention
+        (linear_attention.py:84-85) indexes q_mask whenever kv_mask is given; the cross layers pass x_mask = None with
+        source_mask = query_mask (OnePosePlusModel.py:158-164, transformer.py:160-166), so a masked forward with a cross layer raises
+        TypeError there.  Without a cross layer it would give NaN rows (every logit -inf); that case is refused here."""
+        full = self._full_attention_levels()
+        if not full:
+            return
+        if masked and "loftr_coarse" in full:
+            if "cross" in self.config["loftr_coarse"]["layer_names"]:
+                raise TypeError("full attention with query_image_mask: upstream FullAttention indexes the None q_mask of the cross "
+                                "layers ('NoneType' object is not subscriptable, linear_attention.py:84-85)")
+            raise NotImplementedError("full attention with query_image_mask and self-only layers (NaN rows upstream) is not supported")
+        if self.training:
+            # the autograd graph (train_autograd.py) has linear-attention backward kernels only
+            raise NotImplementedError("full attention: training is not implemented")
 
     def _ensure_ready(self, device, scope=0):
         """scope 1 (training graph): only the raw backbone weights are packed (no BatchNorm folding) -- the other stages read the parameters themselves"""
@@ -500,6 +522,7 @@ class OnePosePlus_model(nn.Module):
             raise NotImplementedError("HIP path supports query_image of shape [B,1,H,W] (got %s)" % (tuple(img.shape),))
         # (the reference returns None and reports through `data`; returning the same dict as well costs nothing and lets wrappers
         # that copy their inputs -- DistributedDataParallel rebuilds every dict it is given -- hand the results back: `out = ddp(d)`)
+        self._check_full_attention("query_image_mask" in data)
         if self.training:
             # training step (lightning_model:54-81): with gradients enabled the forward is built out of autograd nodes whose forward
             # and backward are HIP kernels (train_autograd.py); `conf_matrix` / `expec_f` then carry a grad_fn
@@ -517,6 +540,7 @@ class OnePosePlus_model(nn.Module):
         (linear_attention.py:49-53, coarse_matching.py:108-114) and with the keypoint scaling of batch element 0
         (normalize.py:20-21, quirk q4); the per-sample results are concatenated in batch order, which is the order
         `torch.where` gives the reference (coarse_matching.py:170)."""
+        self._check_full_attention("query_image_mask" in data)
         img = data["query_image"]
         device = img.device
         B = int(img.size(0))
@@ -586,6 +610,7 @@ class OnePosePlus_model(nn.Module):
         coarse level, the training branch of get_coarse_match (coarse_matching.py:177-217: sub-sample the predicted
         matches, pad with ground-truth matches from `conf_matrix_gt`, random draws from `self.train_randint`), fine
         level on the padded match list.  Forward only."""
+        self._check_full_attention("query_image_mask" in data)
         cfg = self.config
         img = data["query_image"]
         device = img.device
