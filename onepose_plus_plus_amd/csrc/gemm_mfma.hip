@@ -8,8 +8,10 @@
 //
 // Design (MI355X-first, not a translated CUDA tiling):
 //  * Three operand arithmetics behind one template (PREC), always fp32 in / fp32 accumulate / fp32 out:
-//      bf16x3 (default)  every operand carried EXACTLY as hi + mid + lo bf16, six v_mfma_f32_32x32x16_bf16 per product
+//      bf16x3 (default)  every operand carried EXACTLY as hi + mid + lo bf16, six bf16 MFMAs per product
 //                        (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi): not narrower than fp32, 2.65x the fp32 MFMA rate;
+//                        convolutions on v_mfma_f32_16x16x32_bf16 (one MFMA per 32-k chunk and 16 x 16 block, r07: the chip holds a
+//                        higher clock on that shape), dense GEMMs on v_mfma_f32_32x32x16_bf16;
 //                        weights pre-split at pack time (48 B per 8 k), activations split on their way to LDS;
 //      fp32              v_mfma_f32_32x32x2_f32, bit-for-bit an fmaf chain (157 TFLOP/s);
 //      fp16x2            narrower than fp32 (hi + lo fp16 pairs, three fp16 MFMAs per product): instantiated in the tuning library only (r06).
@@ -25,7 +27,7 @@
 //  * Software pipeline: register-staged prefetch two chunks ahead, global loads and the LDS hand-over issued ONE PER MFMA
 //    SLOT, the barrier ahead of the last MFMA group so that its skew hides under MFMAs.
 //  * 8-wave tiles (two waves per SIMD) 256x128 / 128x256 / 128x128 / 64x128 / 64x256, 4-wave 64x64; XCD-aware tile order.
-//    128x192 (32x96 per wave) and 128x224 (32x128 | 32x96 per wave on FOUR rotating fragment sets, chunk_ring) for the 196-channel layers.
+//    128x192 (32x96 per wave) and, for dense bf16x3 GEMMs, 128x224 (32x128 | 32x96 per wave on FOUR rotating fragment sets, chunk_ring).
 //  * Epilogue through the idle operand LDS, 16 B per lane: folded-BN bias, residual (direct or bilinear x2
 //    align_corners=True), ReLU / LeakyReLU / elu+1, value scaling, LayerNorm of whole rows, dual-softmax statistics.
 //  * Dense split-K (grid.y) for the weight gradients of the training step (linear_bwd.hip).
@@ -114,7 +116,16 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   // wn = 0 own 4 sub-tiles, those with wn = 1 own 3, and the wave -> (wm, wn) map puts one of each on every SIMD (waves w and w + 4 share
   // SIMD w % 4), so every matrix pipe runs 7 sub-tiles per k-step where the 128 x 256 tile runs 8.  The 32 x 128 wave tile only fits the
   // 256 registers of a two-waves-per-SIMD kernel with FOUR operand fragment sets instead of six: kRing (chunk_ring below).
-  constexpr bool kRing = H3 && kRagged;
+  constexpr bool kRing = H3 && kRagged && !CONV;
+  // bf16x3 CONVOLUTIONS (r07) run on v_mfma_f32_16x16x32_bf16: one MFMA covers a whole 32-k chunk of a 16 x 16 output block, the wave tile
+  // is 2 TM row blocks x NBW column blocks of 16.  The 224-column tile computes 13 blocks (208 columns, the weight rows the loader covers)
+  // on 2 x 4 waves as 7 + 6 blocks per SIMD pair; its columns 208 .. 223 are stored as exact zeros.  Dense bf16x3 GEMMs keep the 32 x 32
+  // loop (chunk_h3 / chunk_ring): the encoder chain and the im2col stem are bit-identical to them.
+  constexpr bool kM16 = H3 && CONV;
+  constexpr int NB16 = kM16 ? kBRowsLoad / 16 : 1;             // computed 16-column blocks of the tile
+  constexpr int NBW = kM16 ? (NB16 + WAVES_N - 1) / WAVES_N : 1;   // per wave (the last wave of a ragged tile owns fewer)
+  constexpr int MB = 2 * TM;                                   // 16-row blocks per wave
+  static_assert(!kM16 || (kBRowsLoad % 16 == 0 && (!kRagged || WAVES_N == 2)), "16 x 16 tile shape");
   static_assert(BM % (WAVES_M * 32) == 0 && BN % 32 == 0, "tile shape");
   static_assert((BM * 8) % NT == 0 && (H3 ? (BN * 12) % NT == 0 || BN == 192 || BN == 224 : (BN * 8) % NT == 0), "load split");
   static_assert(!ASP || !((H3 && ((BN + 31) / 32 % WAVES_N) != 0)), "pre-split activations are not built for the ring tile");
@@ -128,8 +139,9 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  const int wm = __builtin_amdgcn_readfirstlane(kRing ? wave % WAVES_M : wave / WAVES_N);
-  const int wn = __builtin_amdgcn_readfirstlane(kRing ? wave / WAVES_M : wave % WAVES_N);
+  // ragged bf16x3 tiles: waves w and w + 4 (one SIMD) own a long and a short column group
+  const int wm = __builtin_amdgcn_readfirstlane((H3 && kRagged) ? wave % WAVES_M : wave / WAVES_N);
+  const int wn = __builtin_amdgcn_readfirstlane((H3 && kRagged) ? wave / WAVES_M : wave % WAVES_N);
   bool tile_ok[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) tile_ok[j] = kRagged ? (wn * TN + j < NT32) : true;
@@ -159,6 +171,10 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   // byte offset beyond num_records: the buffer unit returns zeros, so there is no exec-masked
   // control flow in the K loop and the loads can be scheduled among the MFMAs.
   constexpr unsigned kOob = 0x80000000u;
+  // 16 x 16 loop: lane l reads row l & 15, k-group l >> 4 of a chunk.  With 52-float rows that is a 2-way bank conflict per ds_read_b128;
+  // swapping the 8-k groups pairwise (0 <-> 1, 2 <-> 3) in rows with bit 2 ^ bit 3 set makes it conflict-free (same LDS size, same pieces)
+  auto kswz = [](int r) -> int { return kM16 ? ((r >> 2) ^ (r >> 3)) & 1 : 0; };
+  auto piece_off = [&](int r, int c) -> int { return r * kLdsStride + (((c / 3) ^ kswz(r)) * 3 + c % 3) * 4; };   // 16-byte piece c = 3 group + part
 
   // byte offset of each load slot's row start (+ this thread's float4); kOob for rows >= M.
   // conv mode: a_mask bit t = tap t of the window falls OUTSIDE the image for this output pixel.
@@ -170,7 +186,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
     const int au = tid + i * NT;
     const int arow = ASP ? au / 12 : lrow + i * (NT / 8);
     const int apiece = ASP ? au - arow * 12 : 0;
-    if constexpr (ASP) a_lds[i] = arow * kLdsStride + apiece * 4;
+    if constexpr (ASP) a_lds[i] = piece_off(arow, apiece);
     const int r = m0 + arow;
     if (CONV) {
       const int ox = r % g.Wout;
@@ -218,7 +234,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       const int n = n0 + row;
       if constexpr (kBFrac) b_base[i] = (n < g.N && u < kBRowsLoad * 12) ? (unsigned)(n * g.ldw + c * 4) * 4u : kOob;
       else b_base[i] = n < g.N ? (unsigned)(n * g.ldw + c * 4) * 4u : kOob;
-      b_lds[i] = row * kLdsStride + c * 4;
+      b_lds[i] = piece_off(row, c);
     } else {
       const int n = n0 + lrow + i * (NT / 8);
       b_base[i] = n < g.N ? (unsigned)(n * g.ldw + kq * 4) * 4u : kOob;
@@ -381,7 +397,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
           lo = hi;
         } else
         split_b3(a_reg[i], hi, mid, lo);
-        float* dst = row + (kq >> 1) * 12 + (kq & 1) * 2;     // group kq/2, elements (kq&1)*4 .. +3 of each part
+        float* dst = row + ((kq >> 1) ^ kswz(lrow + i * (NT / 8))) * 12 + (kq & 1) * 2;     // group kq/2, elements (kq&1)*4 .. +3 of each part
         *reinterpret_cast<uint2*>(dst) = hi;
         *reinterpret_cast<uint2*>(dst + 4) = mid;
         *reinterpret_cast<uint2*>(dst + 8) = lo;
@@ -483,7 +499,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   float4 fa[(H3 && !kRing) ? 6 : 4][TM], fb[(H3 && !kRing) ? 6 : 4][TN];
   float4 da[A_LD], db[B_LD];   // ablation 5 only: load sink that is never consumed in the loop
 
-  if constexpr (kRing) {
+  if constexpr (kRing || kM16) {
     load_global(ga[0], gb[0]);                         // chunk 0 (its weight rows go to LDS below, ahead of the reload of the single set)
   } else {
 #pragma unroll
@@ -492,7 +508,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       load_global(ga[d], gb[d]);
     }
   }
-  if constexpr (kBRowsLoad < BN) {   // weight rows the loader never touches: zero in both buffers
+  if constexpr (kBRowsLoad < BN && !kM16) {   // weight rows the loader never touches: zero in both buffers (the 16 x 16 loop never reads them)
     for (int u = tid; u < 2 * (BN - kBRowsLoad) * kLdsStride; u += NT) {
       const int b = u / ((BN - kBRowsLoad) * kLdsStride), o = u - b * ((BN - kBRowsLoad) * kLdsStride);
       Bs[b * BN * kLdsStride + kBRowsLoad * kLdsStride + o] = 0.f;
@@ -503,10 +519,15 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
     __builtin_amdgcn_sched_barrier(0);
     advance();
     load_global(ga[1], gb[0]);                         // chunk 1: activations into set 1, weights into the single set
+  } else if constexpr (kM16) {
+    __builtin_amdgcn_sched_barrier(0);
+    advance();
+    load_global(ga[0], gb[0]);                         // chunk 1 into the single prefetch set
   }
   __syncthreads();
-  read_frags(0, 0, fa[0], fb[0]);
-  if constexpr (kRing) {
+  if constexpr (!kM16) read_frags(0, 0, fa[0], fb[0]);
+  if constexpr (kM16) {
+  } else if constexpr (kRing) {
     read_frags(0, 1, fa[2], fb[2]);
     read_frags(0, 2, fa[3], fb[3]);
   } else {
@@ -807,6 +828,131 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
+
+  // ---- bf16x3 convolution chunk on v_mfma_f32_16x16x32_bf16 (kM16) ---------------------------------------------------------------------
+  // Per chunk and 16 x 16 block the product order is the one of chunk_h3 (lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi, smallest terms
+  // first, fp32 accumulate); every tile walks K in the same chunk order, so all tiles give the same bits.  The wave tile is cut into four
+  // quadrants (row half h x column half v), each multiplied with all six products at once.  Two quadrant orders alternate over the chunk
+  // pair, so that the fragments of chunk c+1 are read into the registers of the quadrant halves chunk c has finished with -- ONE set of
+  // hi / mid / lo fragments in registers, no second set:
+  //   even chunk:  read B1 A1 | Q00 + LDS hand-over of c+1 | Q01 + global prefetch of c+2 | barrier | read A0' | Q11 | read B1' | Q10
+  //   odd chunk:   read B0 A1 | Q01 + LDS hand-over        | Q00 + global prefetch        | barrier | read A0' | Q10 | read B0' | Q11
+  // (the odd chunk ends with A1, B1 free: the even chunk starts by reading them; the even one ends with A1, B0 free: the odd one reads them).
+  // Half the MFMAs of a chunk sit behind the barrier and cover its skew and the LDS latency of the next chunk's first reads.
+  // ONE global prefetch register set: chunk c+1 leaves it for LDS under the first quadrant, chunk c+2 is loaded into it under the second
+  // (half a chunk of load latency budget, about 1500 cycles at two waves per SIMD); a second set does not fit beside the fragments at
+  // 64 x 64 per wave.
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  constexpr int NBH0 = (NBW + 1) / 2;                      // column blocks of the first column half (the longer one)
+  f32x4 acc4[kM16 ? MB : 1][kM16 ? NBW : 1];
+  float4 fa4[3][kM16 ? MB : 1], fb4[3][kM16 ? NBW : 1];   // part 0 hi, 1 mid, 2 lo
+  if constexpr (kM16) {
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+      for (int j = 0; j < NBW; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const int f16off = (lane & 15) * kLdsStride + (((lane >> 4) ^ kswz(lane & 15)) * 3) * 4;   // block rows start at multiples of 16
+  const int a_frag16 = wm * TM * 32 * kLdsStride + f16off;
+  const int b_frag16 = wn * NBW * 16 * kLdsStride + f16off;
+  auto read_a16 = [&](int buf, auto h_c) {
+    constexpr int H = decltype(h_c)::value;
+    const float* as = As + buf * BM * kLdsStride + a_frag16;
+#pragma unroll
+    for (int i = H * TM; i < H * TM + TM; ++i)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) fa4[p][i] = *reinterpret_cast<const float4*>(as + i * 16 * kLdsStride + p * 4);
+  };
+  auto read_b16 = [&](int buf, auto v_c, auto nbw_c) {
+    constexpr int V = decltype(v_c)::value, NBL = decltype(nbw_c)::value;
+    constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBL : (NBH0 < NBL ? NBH0 : NBL);
+    const float* bs = Bs + buf * BN * kLdsStride + b_frag16;
+#pragma unroll
+    for (int j = j0; j < j1; ++j)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) fb4[p][j] = *reinterpret_cast<const float4*>(bs + j * 16 * kLdsStride + p * 4);
+  };
+  auto quad16 = [&](auto h_c, auto v_c, auto nbw_c, auto&& between) {
+    constexpr int H = decltype(h_c)::value, V = decltype(v_c)::value, NBL = decltype(nbw_c)::value;
+    constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBL : (NBH0 < NBL ? NBH0 : NBL);
+    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
+    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+    int n = 0;
+#pragma unroll
+    for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+      for (int i = H * TM; i < H * TM + TM; ++i)
+#pragma unroll
+        for (int j = j0; j < j1; ++j) {
+          acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_b8(fa4[PA[pr]][i]), as_b8(fb4[PB[pr]][j]), acc4[i][j], 0, 0, 0);
+          between(n);
+          ++n;
+        }
+  };
+  auto chunk_m16 = [&](auto set, int lb, auto nbw_c) {
+    constexpr int P = decltype(set)::value;
+    constexpr int NBL = decltype(nbw_c)::value;
+    constexpr int O = P & 1;                                  // quadrant order: 0 = Q00 Q01 Q11 Q10, 1 = Q01 Q00 Q10 Q11
+    constexpr int kSl0 = 6 * TM * (O ? NBL - NBH0 : (NBH0 < NBL ? NBH0 : NBL));   // MFMA slots of the first quadrant
+    constexpr int kSl1 = 6 * TM * (O ? (NBH0 < NBL ? NBH0 : NBL) : NBL - NBH0);   // ... of the second
+    constexpr int kSt0 = kSl0 / kItems > 0 ? kSl0 / kItems : 1;
+    constexpr int kSt1 = kSl1 / kItems > 0 ? kSl1 / kItems : 1;
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    const int B0 = lb, B1 = lb ^ 1;
+    advance();
+    if (!kNoFrag) {
+      if constexpr (O == 0) read_b16(B0, I1{}, nbw_c);
+      else read_b16(B0, I0{}, nbw_c);
+      read_a16(B0, I1{});
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    auto hand = [&](int n) {                                  // LDS hand-over of chunk c+1 from the single prefetch set
+      if (n % kSt0 == 0 && n / kSt0 < kItems) {
+        if (!kNoLdsSt) store_item(n / kSt0, B1, ga[0], gb[0]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    auto pre = [&](int n) {                                   // global prefetch of chunk c+2 into the same set, one load per slot
+      if (n % kSt1 == 0 && n / kSt1 < kItems) {
+        if (!kNoGload) load_item(n / kSt1, ga[0], gb[0]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if constexpr (O == 0) quad16(I0{}, I0{}, nbw_c, hand);
+    else quad16(I0{}, I1{}, nbw_c, hand);
+#pragma unroll
+    for (int i = kSl0 / kSt0; i < kItems; ++i)
+      if (!kNoLdsSt) store_item(i, B1, ga[0], gb[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (O == 0) quad16(I0{}, I1{}, nbw_c, pre);
+    else quad16(I0{}, I0{}, nbw_c, pre);
+#pragma unroll
+    for (int i = kSl1 / kSt1; i < kItems; ++i)
+      if (!kNoGload) load_item(i, ga[0], gb[0]);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!kNoBar) __syncthreads();
+    if (!kNoFrag) read_a16(B1, I0{});
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (O == 0) quad16(I1{}, I1{}, nbw_c, nothing);
+    else quad16(I1{}, I0{}, nbw_c, nothing);
+    __builtin_amdgcn_sched_barrier(0);
+    if (!kNoFrag) {
+      if constexpr (O == 0) read_b16(B1, I1{}, nbw_c);
+      else read_b16(B1, I0{}, nbw_c);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (O == 0) quad16(I1{}, I0{}, nbw_c, nothing);
+    else quad16(I1{}, I1{}, nbw_c, nothing);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  if constexpr (kM16) {                                      // chunk 0: the first quadrant's fragments
+    if (!kNoFrag) {
+      read_a16(0, std::integral_constant<int, 0>{});
+      read_b16(0, std::integral_constant<int, 0>{}, std::integral_constant<int, NBW>{});
+    }
+  }
+
   if (ABL == 9 || ABL > 90) ts1 = __builtin_readcyclecounter();
   // 8-wave tiles: the second-dispatched half of the workgroup (waves 4-7) is the arbitration loser on every SIMD it shares; one
   // static s_setprio for that half evens the pair out (MI355X_MICROARCH.md, "two waves per SIMD", item 4).  The guard must be
@@ -827,9 +973,24 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       }
     }
   }
+  if constexpr (kM16) {
+    static_assert(DEPTH == 2, "16 x 16 loop: the two quadrant orders alternate over a chunk pair");
+    constexpr int kShort16 = NB16 - (WAVES_N - 1) * NBW;    // live column blocks of the last wave column
+    if (!kRagged || wn != WAVES_N - 1) {                     // wave-uniform; both loops cross the same barriers
+      for (int c = 0; c < nk; c += 2) {
+        chunk_m16(std::integral_constant<int, 0>{}, c & 1, std::integral_constant<int, NBW>{});
+        chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1, std::integral_constant<int, NBW>{});
+      }
+    } else {
+      for (int c = 0; c < nk; c += 2) {
+        chunk_m16(std::integral_constant<int, 0>{}, c & 1, std::integral_constant<int, kShort16>{});
+        chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1, std::integral_constant<int, kShort16>{});
+      }
+    }
+  }
   // nk rounded up to a multiple of DEPTH: the extra chunks are all-zero ones
-  for (int c = 0; c < (kRing ? 0 : nk); c += DEPTH) {
-    if constexpr (kRing) {
+  for (int c = 0; c < ((kRing || kM16) ? 0 : nk); c += DEPTH) {
+    if constexpr (kRing || kM16) {
       // (handled by the two loops above)
     } else if constexpr (H3) {
       chunk_h3(std::integral_constant<int, 0>{}, c & 1);
@@ -866,8 +1027,8 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   // n-subtiles per wave staged per pass: as many as fit the operand buffers
   constexpr int JP = (BM * (WAVES_N * kJPmax * 32 + 4) <= kOperandFloats) ? kJPmax
                      : (BM * (WAVES_N * 2 * 32 + 4) <= kOperandFloats && kJPmax >= 2) ? 2 : 1;
-  constexpr int NPASS = (TN + JP - 1) / JP;
-  constexpr int WP = WAVES_N * JP * 32;                    // staged columns per pass
+  constexpr int NPASS = kM16 ? 1 : (TN + JP - 1) / JP;
+  constexpr int WP = kM16 ? BN : WAVES_N * JP * 32;        // staged columns per pass (16 x 16 loop: the whole tile in one pass)
   constexpr int CS = WP + 4;                               // LDS row stride (floats)
   static_assert((size_t)BM * CS * 4 <= (size_t)2 * (BM + BN) * kLdsStride * 4, "C tile must fit the operand LDS");
   float* Cs = smem;
@@ -875,7 +1036,16 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   const bool vec_ok = g.vec_epilogue != 0;
   // fp16x2: the weight matrix was pre-scaled by a power of two (its fp16 lo halves stay normal); undo, exactly
   const float h2_inv = (H2 && g.h2_inv != nullptr) ? *g.h2_inv : 1.f;
-  if (H2 || scale_on) {   // output scaling once, in place (the statistics below reuse the scaled values)
+  if constexpr (kM16) {
+    if (scale_on) {
+#pragma unroll
+      for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc4[i][j][r] = (acc4[i][j][r] * g.out_mul) / g.out_div;
+    }
+  } else if (H2 || scale_on) {   // output scaling once, in place (the statistics below reuse the scaled values)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -886,7 +1056,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
           acc[i][j][r] = scale_on ? (cv0 * g.out_mul) / g.out_div : cv0;
         }
   }
-  if (g.col_mask != nullptr) {   // masked image cells: sim += -1e9 (coarse_matching.py:108-114); lane = column
+  if (!kM16 && g.col_mask != nullptr) {   // masked image cells (dense score GEMM only): sim += -1e9 (coarse_matching.py:108-114); lane = column
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int col = n0 + wn * TN * 32 + j * 32 + l31;
@@ -912,6 +1082,17 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps) {
     __syncthreads();   // operand buffers (or the previous pass) are no longer read
+    if constexpr (kM16) {
+      // 16 x 16 C layout: col = lane & 15, row = (lane >> 4) * 4 + reg.  Every column of the tile is staged: the blocks the short wave of a
+      // ragged tile does not compute (columns 208 .. 223 of the 224-column tile) stay zero-initialised accumulators -> exact zeros.
+#pragma unroll
+      for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NBW; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            Cs[(wm * TM * 32 + i * 16 + (lane >> 4) * 4 + r) * CS + wn * NBW * 16 + j * 16 + (lane & 15)] = acc4[i][j][r];
+    } else
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -926,7 +1107,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
         }
       }
     __syncthreads();
-    if constexpr (NPASS == 1 && !kRagged && (NT % BM) == 0 && kOperandFloats - BM * CS >= 2 * (NT / BM) * BM + 2 * WAVES_M * WP) {
+    if constexpr (!kM16 && NPASS == 1 && !kRagged && (NT % BM) == 0 && kOperandFloats - BM * CS >= 2 * (NT / BM) * BM + 2 * WAVES_M * WP) {
       if (g.stat_rowmax != nullptr) {
         // fused dual-softmax statistics (coarse_matching.py:115): partial (max, sum exp) of this tile per
         // row (over its columns) and per column (over its rows); merged by tiny kernels.  Every partial is a
@@ -1028,7 +1209,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
         }
       }
     }
-    if constexpr (NPASS == 1 && !kRagged && (WP == 256 || WP == 128)) {
+    if constexpr (!kM16 && NPASS == 1 && !kRagged && (WP == 256 || WP == 128)) {
       if (g.ln_gamma != nullptr) {
         // LayerNorm of the finished rows (the tile spans the row; launcher checks n_store == BN): one wave per
         // row, four rows in lock step, same arithmetic as layernorm_kernel (attention.hip)
@@ -1099,8 +1280,8 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       const int wn2 = lc / (JP * 32);
       const int j = ps * JP + (lc - wn2 * JP * 32) / 32;
       const int row = m0 + lr;
-      const int col = n0 + wn2 * TN * 32 + j * 32 + (lc & 31);
-      if (j >= TN || (kRagged && wn2 * TN + j >= NT32) || row >= g.M || col >= g.n_store) continue;
+      const int col = kM16 ? n0 + lc : n0 + wn2 * TN * 32 + j * 32 + (lc & 31);
+      if ((!kM16 && (j >= TN || (kRagged && wn2 * TN + j >= NT32))) || row >= g.M || col >= g.n_store) continue;
       const float4 cv = *reinterpret_cast<const float4*>(Cs + lr * CS + lc);
       float v[4] = {cv.x, cv.y, cv.z, cv.w};
       const int nval = g.n_store - col < 4 ? g.n_store - col : 4;   // < 4 only on the scalar path
@@ -1298,10 +1479,15 @@ int launch_prec(const OppGemm& g, hipStream_t stream, size_t extra_lds) {
         return OPP_ERR_UNSUPPORTED;
       }
     } else if (g.conv) {
-      auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, true, 0, DEPTH, PREC>;
-      static OppLdsOnce attr_done;
-      set_lds_once(k, lds, attr_done);
-      hipLaunchKernelGGL(k, dim3(tiles, g.k_splits > 1 ? g.k_splits : 1), dim3(NT), lds, stream, g);
+      if constexpr (PREC == OPP_PREC_BF16X3 && BN == 224) {
+        opp_set_error("gemm: bf16x3 convolutions have no 224-column tile (config 27 runs them on 128 x 256)");
+        return OPP_ERR_UNSUPPORTED;
+      } else {
+        auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, true, 0, DEPTH, PREC>;
+        static OppLdsOnce attr_done;
+        set_lds_once(k, lds, attr_done);
+        hipLaunchKernelGGL(k, dim3(tiles, g.k_splits > 1 ? g.k_splits : 1), dim3(NT), lds, stream, g);
+      }
     } else {
       auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, false, 0, DEPTH, PREC>;
       static OppLdsOnce attr_done;
@@ -1638,6 +1824,10 @@ int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
       if (g.prec != OPP_PREC_BF16X3 || g.n_store > 224 || (g.n_real > 208 && g.n_real != g.n_store)) {
         opp_set_error("gemm: tile config 27 (128 x 224) is a bf16x3 tile for outputs of <= 208 real and <= 224 stored columns");
         rc = OPP_ERR_UNSUPPORTED;
+      } else if (g.conv && g.prec == OPP_PREC_BF16X3) {
+        // bf16x3 convolutions run on the 16 x 16 loop, which has no 224-column tile yet (32 x 112 per wave does not fit the registers of a
+        // two-waves-per-SIMD kernel): the 128 x 256 tile of that loop, bit-identical to every other tile
+        rc = launch_cfg<128, 256, 2, 4>(g, stream);
       } else {
         rc = launch_cfg<128, 224, 4, 2>(g, stream);
       }
