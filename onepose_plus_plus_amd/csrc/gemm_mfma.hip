@@ -119,13 +119,17 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   constexpr bool kRing = H3 && kRagged && !CONV;
   // bf16x3 CONVOLUTIONS (r07) run on v_mfma_f32_16x16x32_bf16: one MFMA covers a whole 32-k chunk of a 16 x 16 output block, the wave tile
   // is 2 TM row blocks x NBW column blocks of 16.  The 224-column tile computes 13 blocks (208 columns, the weight rows the loader covers)
-  // on 2 x 4 waves as 7 + 6 blocks per SIMD pair; its columns 208 .. 223 are stored as exact zeros.  Dense bf16x3 GEMMs keep the 32 x 32
-  // loop (chunk_h3 / chunk_ring): the encoder chain and the im2col stem are bit-identical to them.
+  // on two wave roles (kRoles below); its columns 208 .. 223 are stored as exact zeros.  Dense bf16x3 GEMMs keep the 32 x 32 loop
+  // (chunk_h3 / chunk_ring): the encoder chain and the im2col stem are bit-identical to them.
   constexpr bool kM16 = H3 && CONV;
   constexpr int NB16 = kM16 ? kBRowsLoad / 16 : 1;             // computed 16-column blocks of the tile
   constexpr int NBW = kM16 ? (NB16 + WAVES_N - 1) / WAVES_N : 1;   // per wave (the last wave of a ragged tile owns fewer)
-  constexpr int MB = 2 * TM;                                   // 16-row blocks per wave
-  static_assert(!kM16 || (kBRowsLoad % 16 == 0 && (!kRagged || WAVES_N == 2)), "16 x 16 tile shape");
+  // 128 x 224 on 2 x 4 waves (bf16x3 convolutions with <= 208 real columns, the 196-channel layers): 8 row blocks x 13 column blocks on two
+  // wave ROLES instead of a grid.  Role A (waves 0-3): 64 x 64 over columns 0 .. 127, the wave tile of 128 x 256; role B (waves 4-7): 32 rows
+  // (band 32 (w - 4)) x 80 columns over 128 .. 207.  Waves w and w + 4 share SIMD w % 4, so every SIMD runs 16 + 10 = 26 blocks per chunk where
+  // 128 x 256 runs 32, and no wave holds more fragments or accumulators than the 64 x 64 one.
+  constexpr bool kRoles = kM16 && BM == 128 && BN == 224 && WAVES_M == 2 && WAVES_N == 4;
+  static_assert(!kM16 || (kBRowsLoad % 16 == 0 && (!kRagged || WAVES_N == 2 || kRoles)), "16 x 16 tile shape");
   static_assert(BM % (WAVES_M * 32) == 0 && BN % 32 == 0, "tile shape");
   static_assert((BM * 8) % NT == 0 && (H3 ? (BN * 12) % NT == 0 || BN == 192 || BN == 224 : (BN * 8) % NT == 0), "load split");
   static_assert(!ASP || !((H3 && ((BN + 31) / 32 % WAVES_N) != 0)), "pre-split activations are not built for the ring tile");
@@ -214,7 +218,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       a_mask[i] = 0;
     }
   }
-  constexpr bool kRingB = H3 && (NT32 % WAVES_N) != 0;   // (= kRing) the ring tile recomputes these per use: 12 registers it does not have
+  constexpr bool kRingB = kRing;   // the ring tile recomputes these per use: 12 registers it does not have
   unsigned b_base[kRingB ? 1 : B_LD];
   int b_lds[kRingB ? 1 : B_LD];   // LDS float offset of the slot inside the B tile
   auto ring_b = [&](int i, unsigned& base, int& lds) {
@@ -843,121 +847,150 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   // (half a chunk of load latency budget, about 1500 cycles at two waves per SIMD); a second set does not fit beside the fragments at
   // 64 x 64 per wave.
   typedef float f32x4 __attribute__((ext_vector_type(4)));
-  constexpr int NBH0 = (NBW + 1) / 2;                      // column blocks of the first column half (the longer one)
-  f32x4 acc4[kM16 ? MB : 1][kM16 ? NBW : 1];
-  float4 fa4[3][kM16 ? MB : 1], fb4[3][kM16 ? NBW : 1];   // part 0 hi, 1 mid, 2 lo
-  if constexpr (kM16) {
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-      for (int j = 0; j < NBW; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
   const int f16off = (lane & 15) * kLdsStride + (((lane >> 4) ^ kswz(lane & 15)) * 3) * 4;   // block rows start at multiples of 16
-  const int a_frag16 = wm * TM * 32 * kLdsStride + f16off;
-  const int b_frag16 = wn * NBW * 16 * kLdsStride + f16off;
-  auto read_a16 = [&](int buf, auto h_c) {
-    constexpr int H = decltype(h_c)::value;
-    const float* as = As + buf * BM * kLdsStride + a_frag16;
-#pragma unroll
-    for (int i = H * TM; i < H * TM + TM; ++i)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) fa4[p][i] = *reinterpret_cast<const float4*>(as + i * 16 * kLdsStride + p * 4);
+  auto loop_start = [&]() {
+    if (ABL == 9 || ABL > 90) ts1 = __builtin_readcyclecounter();
+    // 8-wave tiles: the second-dispatched half of the workgroup (waves 4-7) is the arbitration loser on every SIMD it shares; one
+    // static s_setprio for that half evens the pair out (MI355X_MICROARCH.md, "two waves per SIMD", item 4).  The guard must be
+    // provably wave-uniform: s_setprio ignores EXEC.
+    if (NT == 512 && (g.xcd_swizzle & 2) && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
   };
-  auto read_b16 = [&](int buf, auto v_c, auto nbw_c) {
-    constexpr int V = decltype(v_c)::value, NBL = decltype(nbw_c)::value;
-    constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBL : (NBH0 < NBL ? NBH0 : NBL);
-    const float* bs = Bs + buf * BN * kLdsStride + b_frag16;
+  // One wave tile of the 16 x 16 loop: 2 TMW row blocks from tile row arow0 x NBWW column blocks from tile column bcol0, of which the first
+  // NBLW are computed.  Runs the K loop, then stages the accumulators in the C tile of the epilogue (row stride BN + 4) behind the barrier
+  // that ends the operand reads; blocks it does not compute are staged as exact zeros.  Each call site sits behind a wave-uniform branch, and
+  // every call crosses the same barriers.
+  auto m16_tile = [&](auto tm_c, auto nbw_c, auto nbl_c, int arow0, int bcol0) __attribute__((always_inline)) {
+    constexpr int TMW = decltype(tm_c)::value, NBWW = decltype(nbw_c)::value, NBLW = decltype(nbl_c)::value;
+    constexpr int MBW = 2 * TMW;                              // 16-row blocks of the wave tile
+    constexpr int NBH0 = (NBWW + 1) / 2;                      // column blocks of the first column half (the longer one)
+    f32x4 acc4[MBW][NBWW];
+    float4 fa4[3][MBW], fb4[3][NBWW];                         // part 0 hi, 1 mid, 2 lo
 #pragma unroll
-    for (int j = j0; j < j1; ++j)
+    for (int i = 0; i < MBW; ++i)
 #pragma unroll
-      for (int p = 0; p < 3; ++p) fb4[p][j] = *reinterpret_cast<const float4*>(bs + j * 16 * kLdsStride + p * 4);
-  };
-  auto quad16 = [&](auto h_c, auto v_c, auto nbw_c, auto&& between) {
-    constexpr int H = decltype(h_c)::value, V = decltype(v_c)::value, NBL = decltype(nbw_c)::value;
-    constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBL : (NBH0 < NBL ? NBH0 : NBL);
-    constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
-    constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
-    int n = 0;
+      for (int j = 0; j < NBWW; ++j) acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int a_frag16 = arow0 * kLdsStride + f16off;
+    const int b_frag16 = bcol0 * kLdsStride + f16off;
+    auto read_a16 = [&](int buf, auto h_c) {
+      constexpr int H = decltype(h_c)::value;
+      const float* as = As + buf * BM * kLdsStride + a_frag16;
 #pragma unroll
-    for (int pr = 0; pr < 6; ++pr)
+      for (int i = H * TMW; i < H * TMW + TMW; ++i)
 #pragma unroll
-      for (int i = H * TM; i < H * TM + TM; ++i)
+        for (int p = 0; p < 3; ++p) fa4[p][i] = *reinterpret_cast<const float4*>(as + i * 16 * kLdsStride + p * 4);
+    };
+    auto read_b16 = [&](int buf, auto v_c) {
+      constexpr int V = decltype(v_c)::value;
+      constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBLW : (NBH0 < NBLW ? NBH0 : NBLW);
+      const float* bs = Bs + buf * BN * kLdsStride + b_frag16;
 #pragma unroll
-        for (int j = j0; j < j1; ++j) {
-          acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_b8(fa4[PA[pr]][i]), as_b8(fb4[PB[pr]][j]), acc4[i][j], 0, 0, 0);
-          between(n);
-          ++n;
+      for (int j = j0; j < j1; ++j)
+#pragma unroll
+        for (int p = 0; p < 3; ++p) fb4[p][j] = *reinterpret_cast<const float4*>(bs + j * 16 * kLdsStride + p * 4);
+    };
+    auto quad16 = [&](auto h_c, auto v_c, auto&& between) {
+      constexpr int H = decltype(h_c)::value, V = decltype(v_c)::value;
+      constexpr int j0 = V ? NBH0 : 0, j1 = V ? NBLW : (NBH0 < NBLW ? NBH0 : NBLW);
+      constexpr int PA[6] = {2, 0, 1, 1, 0, 0};
+      constexpr int PB[6] = {0, 2, 1, 0, 1, 0};
+      int n = 0;
+#pragma unroll
+      for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+        for (int i = H * TMW; i < H * TMW + TMW; ++i)
+#pragma unroll
+          for (int j = j0; j < j1; ++j) {
+            acc4[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_b8(fa4[PA[pr]][i]), as_b8(fb4[PB[pr]][j]), acc4[i][j], 0, 0, 0);
+            between(n);
+            ++n;
+          }
+    };
+    auto chunk_m16 = [&](auto set, int lb) {
+      constexpr int P = decltype(set)::value;
+      constexpr int O = P & 1;                                  // quadrant order: 0 = Q00 Q01 Q11 Q10, 1 = Q01 Q00 Q10 Q11
+      constexpr int kSl0 = 6 * TMW * (O ? NBLW - NBH0 : (NBH0 < NBLW ? NBH0 : NBLW));   // MFMA slots of the first quadrant
+      constexpr int kSl1 = 6 * TMW * (O ? (NBH0 < NBLW ? NBH0 : NBLW) : NBLW - NBH0);   // ... of the second
+      constexpr int kSt0 = kSl0 / kItems > 0 ? kSl0 / kItems : 1;
+      constexpr int kSt1 = kSl1 / kItems > 0 ? kSl1 / kItems : 1;
+      using I0 = std::integral_constant<int, 0>;
+      using I1 = std::integral_constant<int, 1>;
+      const int B0 = lb, B1 = lb ^ 1;
+      advance();
+      if (!kNoFrag) {
+        if constexpr (O == 0) read_b16(B0, I1{});
+        else read_b16(B0, I0{});
+        read_a16(B0, I1{});
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      auto hand = [&](int n) {                                  // LDS hand-over of chunk c+1 from the single prefetch set
+        if (n % kSt0 == 0 && n / kSt0 < kItems) {
+          if (!kNoLdsSt) store_item(n / kSt0, B1, ga[0], gb[0]);
+          __builtin_amdgcn_sched_barrier(0);
         }
-  };
-  auto chunk_m16 = [&](auto set, int lb, auto nbw_c) {
-    constexpr int P = decltype(set)::value;
-    constexpr int NBL = decltype(nbw_c)::value;
-    constexpr int O = P & 1;                                  // quadrant order: 0 = Q00 Q01 Q11 Q10, 1 = Q01 Q00 Q10 Q11
-    constexpr int kSl0 = 6 * TM * (O ? NBL - NBH0 : (NBH0 < NBL ? NBH0 : NBL));   // MFMA slots of the first quadrant
-    constexpr int kSl1 = 6 * TM * (O ? (NBH0 < NBL ? NBH0 : NBL) : NBL - NBH0);   // ... of the second
-    constexpr int kSt0 = kSl0 / kItems > 0 ? kSl0 / kItems : 1;
-    constexpr int kSt1 = kSl1 / kItems > 0 ? kSl1 / kItems : 1;
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    const int B0 = lb, B1 = lb ^ 1;
-    advance();
-    if (!kNoFrag) {
-      if constexpr (O == 0) read_b16(B0, I1{}, nbw_c);
-      else read_b16(B0, I0{}, nbw_c);
-      read_a16(B0, I1{});
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    auto hand = [&](int n) {                                  // LDS hand-over of chunk c+1 from the single prefetch set
-      if (n % kSt0 == 0 && n / kSt0 < kItems) {
-        if (!kNoLdsSt) store_item(n / kSt0, B1, ga[0], gb[0]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    auto pre = [&](int n) {                                   // global prefetch of chunk c+2 into the same set, one load per slot
-      if (n % kSt1 == 0 && n / kSt1 < kItems) {
-        if (!kNoGload) load_item(n / kSt1, ga[0], gb[0]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    if constexpr (O == 0) quad16(I0{}, I0{}, nbw_c, hand);
-    else quad16(I0{}, I1{}, nbw_c, hand);
+      };
+      auto pre = [&](int n) {                                   // global prefetch of chunk c+2 into the same set, one load per slot
+        if (n % kSt1 == 0 && n / kSt1 < kItems) {
+          if (!kNoGload) load_item(n / kSt1, ga[0], gb[0]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if constexpr (O == 0) quad16(I0{}, I0{}, hand);
+      else quad16(I0{}, I1{}, hand);
 #pragma unroll
-    for (int i = kSl0 / kSt0; i < kItems; ++i)
-      if (!kNoLdsSt) store_item(i, B1, ga[0], gb[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (O == 0) quad16(I0{}, I1{}, nbw_c, pre);
-    else quad16(I0{}, I0{}, nbw_c, pre);
+      for (int i = kSl0 / kSt0; i < kItems; ++i)
+        if (!kNoLdsSt) store_item(i, B1, ga[0], gb[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (O == 0) quad16(I0{}, I1{}, pre);
+      else quad16(I0{}, I0{}, pre);
 #pragma unroll
-    for (int i = kSl1 / kSt1; i < kItems; ++i)
-      if (!kNoGload) load_item(i, ga[0], gb[0]);
-    __builtin_amdgcn_sched_barrier(0);
-    if (!kNoBar) __syncthreads();
-    if (!kNoFrag) read_a16(B1, I0{});
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (O == 0) quad16(I1{}, I1{}, nbw_c, nothing);
-    else quad16(I1{}, I0{}, nbw_c, nothing);
-    __builtin_amdgcn_sched_barrier(0);
-    if (!kNoFrag) {
-      if constexpr (O == 0) read_b16(B1, I1{}, nbw_c);
-      else read_b16(B1, I0{}, nbw_c);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (O == 0) quad16(I1{}, I0{}, nbw_c, nothing);
-    else quad16(I1{}, I1{}, nbw_c, nothing);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  if constexpr (kM16) {                                      // chunk 0: the first quadrant's fragments
-    if (!kNoFrag) {
+      for (int i = kSl1 / kSt1; i < kItems; ++i)
+        if (!kNoGload) load_item(i, ga[0], gb[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      if (!kNoBar) __syncthreads();
+      if (!kNoFrag) read_a16(B1, I0{});
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (O == 0) quad16(I1{}, I1{}, nothing);
+      else quad16(I1{}, I0{}, nothing);
+      __builtin_amdgcn_sched_barrier(0);
+      if (!kNoFrag) {
+        if constexpr (O == 0) read_b16(B1, I1{});
+        else read_b16(B1, I0{});
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (O == 0) quad16(I1{}, I0{}, nothing);
+      else quad16(I1{}, I1{}, nothing);
+      __builtin_amdgcn_sched_barrier(0);
+    };
+    if (!kNoFrag) {                                             // chunk 0: the first quadrant's fragments
       read_a16(0, std::integral_constant<int, 0>{});
-      read_b16(0, std::integral_constant<int, 0>{}, std::integral_constant<int, NBW>{});
+      read_b16(0, std::integral_constant<int, 0>{});
     }
-  }
+    loop_start();
+    for (int c = 0; c < nk; c += 2) {
+      chunk_m16(std::integral_constant<int, 0>{}, c & 1);
+      chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1);
+    }
+    if (ABL == 9 || ABL > 90) ts2 = __builtin_readcyclecounter();
+    if (g.out_mul != 1.f || g.out_div != 1.f) {                 // output scaling once, in place
+#pragma unroll
+      for (int i = 0; i < MBW; ++i)
+#pragma unroll
+        for (int j = 0; j < NBWW; ++j)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) acc4[i][j][r] = (acc4[i][j][r] * g.out_mul) / g.out_div;
+    }
+    __syncthreads();   // the operand buffers are no longer read
+    // 16 x 16 C layout: col = lane & 15, row = (lane >> 4) * 4 + reg
+#pragma unroll
+    for (int i = 0; i < MBW; ++i)
+#pragma unroll
+      for (int j = 0; j < NBWW; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          smem[(arow0 + i * 16 + (lane >> 4) * 4 + r) * (BN + 4) + bcol0 + j * 16 + (lane & 15)] = acc4[i][j][r];
+  };
 
-  if (ABL == 9 || ABL > 90) ts1 = __builtin_readcyclecounter();
-  // 8-wave tiles: the second-dispatched half of the workgroup (waves 4-7) is the arbitration loser on every SIMD it shares; one
-  // static s_setprio for that half evens the pair out (MI355X_MICROARCH.md, "two waves per SIMD", item 4).  The guard must be
-  // provably wave-uniform: s_setprio ignores EXEC.
-  if (NT == 512 && (g.xcd_swizzle & 2) && __builtin_amdgcn_readfirstlane(tid) >= 256) __builtin_amdgcn_s_setprio(1);
+  if constexpr (!kM16) loop_start();
   if constexpr (kRing) {
     constexpr int kFull = TN, kShort = NT32 - (WAVES_N - 1) * TN;     // live sub-tiles of the waves with wn < WAVES_N - 1 / of the last ones
     static_assert(DEPTH == 2 && kShort >= 1 && kShort <= TN, "ring tile");
@@ -975,17 +1008,25 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   }
   if constexpr (kM16) {
     static_assert(DEPTH == 2, "16 x 16 loop: the two quadrant orders alternate over a chunk pair");
-    constexpr int kShort16 = NB16 - (WAVES_N - 1) * NBW;    // live column blocks of the last wave column
-    if (!kRagged || wn != WAVES_N - 1) {                     // wave-uniform; both loops cross the same barriers
-      for (int c = 0; c < nk; c += 2) {
-        chunk_m16(std::integral_constant<int, 0>{}, c & 1, std::integral_constant<int, NBW>{});
-        chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1, std::integral_constant<int, NBW>{});
-      }
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    using I4 = std::integral_constant<int, 4>;
+    using I5 = std::integral_constant<int, 5>;
+    if constexpr (kRoles) {
+      static_assert(TM == 2 && NB16 == 13, "two-role tile: 64 x 64 waves over columns 0 .. 127, 32 x 80 waves over 128 .. 207");
+      const int w = __builtin_amdgcn_readfirstlane(wave);    // wave-uniform: both roles cross the same barriers
+      if (w < 4) m16_tile(I2{}, I4{}, I4{}, 64 * (w & 1), 64 * (w >> 1));
+      else m16_tile(I1{}, I5{}, I5{}, 32 * (w - 4), 128);
+      // columns 208 .. 223 (no role computes them): exact zeros, like the zero-weight columns of the 128 x 256 tile
+      constexpr int kZq = (BN - NB16 * 16) / 4;                 // float4 per row
+      for (int u = tid; u < BM * kZq; u += NT)
+        *reinterpret_cast<float4*>(smem + (u / kZq) * (BN + 4) + NB16 * 16 + (u % kZq) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     } else {
-      for (int c = 0; c < nk; c += 2) {
-        chunk_m16(std::integral_constant<int, 0>{}, c & 1, std::integral_constant<int, kShort16>{});
-        chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1, std::integral_constant<int, kShort16>{});
-      }
+      constexpr int kShort16 = NB16 - (WAVES_N - 1) * NBW;    // live column blocks of the last wave column
+      using IT = std::integral_constant<int, TM>;
+      using IW = std::integral_constant<int, NBW>;
+      if (!kRagged || wn != WAVES_N - 1) m16_tile(IT{}, IW{}, IW{}, wm * TM * 32, wn * NBW * 16);   // wave-uniform
+      else m16_tile(IT{}, IW{}, std::integral_constant<int, kShort16>{}, wm * TM * 32, wn * NBW * 16);
     }
   }
   // nk rounded up to a multiple of DEPTH: the extra chunks are all-zero ones
@@ -1009,7 +1050,7 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       if (DEPTH > 3) chunk(std::integral_constant<int, 3 % DEPTH>{}, (c + 3) & 1);
     }
   }
-  if (ABL == 9 || ABL > 90) ts2 = __builtin_readcyclecounter();
+  if (!kM16 && (ABL == 9 || ABL > 90)) ts2 = __builtin_readcyclecounter();
   if (ABL == 5) {
 #pragma unroll
     for (int i = 0; i < A_LD; ++i) asm volatile("" ::"v"(da[i].x), "v"(da[i].w));
@@ -1031,21 +1072,13 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   constexpr int WP = kM16 ? BN : WAVES_N * JP * 32;        // staged columns per pass (16 x 16 loop: the whole tile in one pass)
   constexpr int CS = WP + 4;                               // LDS row stride (floats)
   static_assert((size_t)BM * CS * 4 <= (size_t)2 * (BM + BN) * kLdsStride * 4, "C tile must fit the operand LDS");
+  static_assert(!kM16 || CS == BN + 4, "the 16 x 16 loop stages its accumulators with row stride BN + 4 (m16_tile)");
   float* Cs = smem;
   const bool scale_on = (g.out_mul != 1.f) || (g.out_div != 1.f);
   const bool vec_ok = g.vec_epilogue != 0;
   // fp16x2: the weight matrix was pre-scaled by a power of two (its fp16 lo halves stay normal); undo, exactly
   const float h2_inv = (H2 && g.h2_inv != nullptr) ? *g.h2_inv : 1.f;
-  if constexpr (kM16) {
-    if (scale_on) {
-#pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NBW; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc4[i][j][r] = (acc4[i][j][r] * g.out_mul) / g.out_div;
-    }
-  } else if (H2 || scale_on) {   // output scaling once, in place (the statistics below reuse the scaled values)
+  if (!kM16 && (H2 || scale_on)) {   // output scaling once, in place (the statistics below reuse the scaled values; 16 x 16 loop: m16_tile)
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1081,20 +1114,10 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   }
 #pragma unroll
   for (int ps = 0; ps < NPASS; ++ps) {
-    __syncthreads();   // operand buffers (or the previous pass) are no longer read
-    if constexpr (kM16) {
-      // 16 x 16 C layout: col = lane & 15, row = (lane >> 4) * 4 + reg.  Every column of the tile is staged: the blocks the short wave of a
-      // ragged tile does not compute (columns 208 .. 223 of the 224-column tile) stay zero-initialised accumulators -> exact zeros.
+    // (the 16 x 16 loop has staged every column of its tile already, behind its own barrier: m16_tile)
+    if constexpr (!kM16) __syncthreads();   // operand buffers (or the previous pass) are no longer read
 #pragma unroll
-      for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NBW; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            Cs[(wm * TM * 32 + i * 16 + (lane >> 4) * 4 + r) * CS + wn * NBW * 16 + j * 16 + (lane & 15)] = acc4[i][j][r];
-    } else
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < (kM16 ? 0 : TM); ++i)
 #pragma unroll
       for (int jj = 0; jj < JP; ++jj) {
         const int j = ps * JP + jj;
@@ -1459,7 +1482,7 @@ int launch_prec(const OppGemm& g, hipStream_t stream, size_t extra_lds) {
   // (fp16x2 keeps the 4-wave 128x128 tile: its score GEMM with the fused statistics runs on it)
   // 128 x 192 on 8 waves (32 x 96 per wave, 219 registers, 133 KB of LDS): the 192-column body of the 196-channel layers, whose last 4
   // columns come from conv_tail.hip (round 5; config 24)
-  constexpr bool kNarrowB3 = BM == 128 && (BN == 192 || BN == 224) && NT == 512 && PREC == OPP_PREC_BF16X3;   // (and the 224-column ring tile)
+  constexpr bool kNarrowB3 = BM == 128 && (BN == 192 || BN == 224) && NT == 512 && PREC == OPP_PREC_BF16X3;   // (and the 224-column tiles)
   constexpr bool ok = (PREC == OPP_PREC_FP32 && BN != 192 && BN != 224) ||
                       (DEPTH == 2 && (NT == 512 || (BM == 64 && BN == 64) || (PREC == OPP_PREC_FP16X2 && BM == 128 && BN == 128)) &&
                        (BN == 128 || BN == 64 || BN == 256 || kNarrowB3) &&
@@ -1479,8 +1502,8 @@ int launch_prec(const OppGemm& g, hipStream_t stream, size_t extra_lds) {
         return OPP_ERR_UNSUPPORTED;
       }
     } else if (g.conv) {
-      if constexpr (PREC == OPP_PREC_BF16X3 && BN == 224) {
-        opp_set_error("gemm: bf16x3 convolutions have no 224-column tile (config 27 runs them on 128 x 256)");
+      if constexpr (PREC == OPP_PREC_BF16X3 && BN == 224 && WAVES_N != 4) {
+        opp_set_error("gemm: the 128 x 224 ring tile is built for dense GEMMs only");
         return OPP_ERR_UNSUPPORTED;
       } else {
         auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, true, 0, DEPTH, PREC>;
@@ -1489,10 +1512,15 @@ int launch_prec(const OppGemm& g, hipStream_t stream, size_t extra_lds) {
         hipLaunchKernelGGL(k, dim3(tiles, g.k_splits > 1 ? g.k_splits : 1), dim3(NT), lds, stream, g);
       }
     } else {
-      auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, false, 0, DEPTH, PREC>;
-      static OppLdsOnce attr_done;
-      set_lds_once(k, lds, attr_done);
-      hipLaunchKernelGGL(k, dim3(tiles, g.k_splits > 1 ? g.k_splits : 1), dim3(NT), lds, stream, g);
+      if constexpr (BN == 224 && WAVES_N == 4) {
+        opp_set_error("gemm: the 128 x 224 two-role tile is built for bf16x3 convolutions only");
+        return OPP_ERR_UNSUPPORTED;
+      } else {
+        auto k = opp_gemm_kernel<BM, BN, WAVES_M, WAVES_N, false, 0, DEPTH, PREC>;
+        static OppLdsOnce attr_done;
+        set_lds_once(k, lds, attr_done);
+        hipLaunchKernelGGL(k, dim3(tiles, g.k_splits > 1 ? g.k_splits : 1), dim3(NT), lds, stream, g);
+      }
     }
     OPP_CHECK_LAUNCH("opp_gemm_kernel");
     return OPP_OK;
@@ -1653,8 +1681,9 @@ static int choose_tile(const OppGemm& g) {
     struct Cand { int cfg, bm, bn, wpc, chunk, fixed; };
     // (24: 128 x 192, for outputs that are whole 192-column tiles -- the body of a 196-channel layer: measured 228 us against 272 on the
     // 128 x 256 tile at 256 x 256 pixels, profiles/r05_conv_bench_192_columns.txt)
-    // (27: 128 x 224 on four fragment sets, for outputs of exactly 224 stored columns -- the 196-channel layers in one column tile,
-    // 7 sub-tiles per SIMD and k-step instead of the 8 of 128 x 256)
+    // (27: 128 x 224 for outputs of exactly 224 stored columns -- the 196-channel layers in one column tile: dense GEMMs on four fragment
+    // sets, 7 sub-tiles per SIMD and k-step instead of the 8 of 128 x 256; convolutions on two wave roles, 26 blocks per SIMD and chunk
+    // instead of 32)
     static const Cand cands[] = {{24, 128, 192, 1, 4000, 16000}, {27, 128, 224, 1, 4250, 16000}, {22, 128, 256, 1, 4800, 16000}, {20, 256, 128, 1, 4800, 16000},
                                  {25, 128, 128, 1, 2600, 13000}, {26, 64, 128, 2, 1400, 11000},
                                  {2, 64, 64, 3, 1000, 9000}};
@@ -1700,6 +1729,12 @@ static int choose_tile(const OppGemm& g) {
     }
   }
   return cfg;
+}
+
+// a bf16x3 convolution whose weight rows >= 208 are known to be zero padding (<= 208 real of <= 224 stored columns): config 22 runs it on the
+// two-role 128 x 224 tile.  Unknown real counts (n_real == 0), pre-split activations and K slices keep 128 x 256.
+static bool conv208(const OppGemm& g) {
+  return g.conv && g.prec == OPP_PREC_BF16X3 && !g.a_split && g.k_splits <= 1 && g.n_real > 0 && g.n_real <= 208 && g.n_store <= 224;
 }
 
 int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
@@ -1816,7 +1851,11 @@ int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
     case 10: rc = launch_cfg<128, 128, 2, 2, 3>(g, stream); break;  // deeper global prefetch (long-K fp32 convs)
     case 11: rc = launch_cfg<128, 128, 2, 2, 4>(g, stream); break;
     case 20: rc = launch_cfg<256, 128, 4, 2>(g, stream); break;     // 8 waves: two per SIMD
-    case 22: rc = launch_cfg<128, 256, 2, 4>(g, stream); break;
+    case 22:
+      // bf16x3 convolutions of <= 208 known real columns (the 196-channel layers): the two-role 128 x 224 tile, 26 instead of 32 blocks per
+      // SIMD and chunk, bit-identical to 128 x 256 (columns 208 .. 223 stored as the zeros 128 x 256 computes there)
+      rc = conv208(g) ? launch_cfg<128, 224, 2, 4>(g, stream) : launch_cfg<128, 256, 2, 4>(g, stream);
+      break;
     case 24: rc = launch_cfg<128, 192, 4, 2>(g, stream); break;     // 8 waves, 32x96 per wave: 192-column bodies of the 196-channel layers
     case 25: rc = launch_cfg<128, 128, 4, 2>(g, stream); break;     // 8 waves, 32x64 per wave (M ~ 16k layers)
     case 27:
@@ -1824,14 +1863,15 @@ int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
       if (g.prec != OPP_PREC_BF16X3 || g.n_store > 224 || (g.n_real > 208 && g.n_real != g.n_store)) {
         opp_set_error("gemm: tile config 27 (128 x 224) is a bf16x3 tile for outputs of <= 208 real and <= 224 stored columns");
         rc = OPP_ERR_UNSUPPORTED;
-      } else if (g.conv && g.prec == OPP_PREC_BF16X3) {
-        // bf16x3 convolutions run on the 16 x 16 loop, which has no 224-column tile yet (32 x 112 per wave does not fit the registers of a
-        // two-waves-per-SIMD kernel): the 128 x 256 tile of that loop, bit-identical to every other tile
-        rc = launch_cfg<128, 256, 2, 4>(g, stream);
+      } else if (g.conv && (g.a_split || g.k_splits > 1)) {
+        rc = launch_cfg<128, 256, 2, 4>(g, stream);   // the two-role tile is not built for pre-split activations; K slices keep 128 x 256
+      } else if (g.conv) {
+        // bf16x3 convolutions: the two-role 128 x 224 tile of the 16 x 16 loop (64 x 64 | 32 x 80 per wave, see opp_gemm_body)
+        rc = launch_cfg<128, 224, 2, 4>(g, stream);
       } else {
-        rc = launch_cfg<128, 224, 4, 2>(g, stream);
+        rc = launch_cfg<128, 224, 4, 2>(g, stream);   // dense: 8 waves, 32 x 128 | 32 x 96 per wave, four fragment sets
       }
-      break;   // 8 waves, 32 x 128 | 32 x 96 per wave, four fragment sets
+      break;
     case 26: rc = launch_cfg<64, 128, 2, 4>(g, stream); break;      // 8 waves, 32x32 per wave
     case 30: rc = launch_cfg<64, 256, 2, 4>(g, stream); break;      // 8 waves, full 256-column rows (fused LayerNorm)
     default:
