@@ -512,6 +512,20 @@ int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_points, const d
                    double reproj_error_px, double scale, int iterations, unsigned seed,
                    int refine_iters, double* pose_out, int* inlier_mask, int* n_inliers, int* ok,
                    void* workspace, size_t workspace_bytes, void* stream);
+/* The same with a choice of minimal solver and OpenCV's adaptive stop.  solver 0 = P3P + Gauss-Newton (opp_pnp_ransac;
+ * identical to it when confidence >= 1), 1 = EPnP as in cv2.solvePnPRansac(flags=SOLVEPNP_EPNP): 5-match EPnP hypotheses
+ * (P3P when n == 4, one EPnP solve on all points when n == 5), an EPnP refit on the best hypothesis's RANSAC inliers, which
+ * are the inliers returned (refine_iters is ignored).  confidence (OpenCV default 0.99; >= 1: never stop early) sets
+ * niters = RANSACUpdateNumIters after each new best; the result is that of the sequential loop over hypotheses 0, 1, ...
+ * Extra device outputs: stop_out (1 int: hypotheses the sequential loop evaluates), and, when not NULL, samples_out
+ * [iterations][5] (sample indices; -1 in the 5th column for P3P) and scores_out [iterations] (inlier counts, -1 = no model),
+ * written whenever hypotheses are drawn (n >= 4; with solver 1 not for n == 5). */
+size_t opp_pnp_ex_workspace_bytes(int iterations, int n_points);
+int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, const double* K4,
+                      double reproj_error_px, double scale, int iterations, unsigned seed,
+                      int refine_iters, int solver, double confidence, double* pose_out, int* inlier_mask,
+                      int* n_inliers, int* ok, int* stop_out, int* samples_out, int* scores_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* Tuning aid (libraries built with -DOPP_TUNING only; otherwise returns an error): device buffer (4 x uint64 per
  * wave) for the phase time stamps written by the timed conv variants (tile_cfg 120 = 256x128 / 8 waves,

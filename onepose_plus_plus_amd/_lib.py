@@ -142,6 +142,10 @@ SIGNATURES = {
     "opp_pnp_ransac": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
                                c_int, ctypes.c_uint, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    "opp_pnp_ex_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "opp_pnp_ransac_ex": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
+                                  c_int, ctypes.c_uint, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_backbone_tape_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "opp_backbone_train_tape_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "opp_backbone_train_tape": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

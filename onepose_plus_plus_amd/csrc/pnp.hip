@@ -12,6 +12,14 @@
 //   2. scoring    : one wave per hypothesis counts reprojection inliers over all matches
 //   3. selection  : arg-max inlier count (ties -> lowest hypothesis index: deterministic)
 //   4. refinement : Gauss-Newton on the inlier set (re-evaluated every iteration), one workgroup
+//
+// opp_pnp_ransac_ex adds the reference's own estimator (solver 1, EPnP as in cv2.solvePnPRansac(flags=SOLVEPNP_EPNP)):
+//   1. hypotheses : one wave per hypothesis: 5 distinct matches (same hash RNG), EPnP (pnp_math.h) with M^T M, its 12x12
+//                   Jacobi and every other array in LDS (no scratch); n == 4 runs the P3P hypotheses above (OpenCV's switch)
+//   2. scoring    : pnp_score_kernel, unchanged
+//   3. final      : one workgroup: the sequential RANSAC loop over the scores with OpenCV's adaptive stop (a scan of the
+//                   per-hypothesis counts in index order, skipping 256ths of the range whose maximum cannot be a new best),
+//                   the best hypothesis's inlier mask, and an EPnP refit on those inliers (reductions in point order)
 #include "opp_common.h"
 #include "pnp_math.h"
 
@@ -234,6 +242,240 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const float* __restrict
   }
 }
 
+
+// ---- EPnP (opp_pnp_ransac_ex, solver 1) ------------------------------------------------------------------------------
+
+// the sampling of pnp_hypotheses_kernel, drawing K distinct indices
+template <int K>
+__device__ __forceinline__ void draw_sample(unsigned seed, int h, int n, int* idx) {
+  unsigned s = hash32(seed ^ (0x9e3779b9u * (unsigned)(h + 1)));
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    for (int tries = 0; tries < 64; ++tries) {
+      s = hash32(s + 0x632be5abu);
+      const int c = (int)(s % (unsigned)n);
+      bool dup = false;
+#pragma unroll
+      for (int j = 0; j < k; ++j) dup |= idx[j] == c;
+      idx[k] = c;
+      if (!dup) break;
+    }
+  }
+}
+
+// sample indices of the P3P hypotheses (4 per hypothesis, the 5th column -1), for opp_pnp_ransac_ex's optional output
+__global__ __launch_bounds__(256) void pnp_p3p_samples_kernel(PnpParams prm, int* __restrict__ samples) {
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= prm.iters) return;
+  int idx[4];
+  draw_sample<4>(prm.seed, h, prm.n, idx);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) samples[(size_t)h * 5 + k] = idx[k];
+  samples[(size_t)h * 5 + 4] = -1;
+}
+
+// one 64-thread workgroup (one wave) per hypothesis: 5 distinct matches -> EPnP -> hyp[h] (R | t), valid[h]
+__global__ __launch_bounds__(64) void pnp_epnp_hypotheses_kernel(const float* __restrict__ p2, const float* __restrict__ p3, PnpParams prm,
+                                                                 double* __restrict__ hyp, int* __restrict__ valid, int* __restrict__ samples) {
+  __shared__ OppEpnpWs w;
+  __shared__ double sX[15], suv[10], salph[20], spcs[15], sperr[5], sK[4];
+  __shared__ int sidx[5], sdistinct;
+  const int h = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    int idx[5];
+    draw_sample<5>(prm.seed, h, prm.n, idx);
+    bool distinct = true;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      sidx[k] = idx[k];
+#pragma unroll
+      for (int j = 0; j < k; ++j) distinct &= idx[j] != idx[k];
+    }
+    sdistinct = distinct ? 1 : 0;
+    if (samples) {
+#pragma unroll
+      for (int k = 0; k < 5; ++k) samples[(size_t)h * 5 + k] = idx[k];
+    }
+  }
+  if (tid < 4) sK[tid] = prm.K4[tid];
+  __syncthreads();
+  if (tid < 5) {
+    const int i = sidx[tid];
+    for (int c = 0; c < 3; ++c) sX[3 * tid + c] = (double)p3[3 * i + c] * prm.scale;
+    suv[2 * tid] = (double)p2[2 * i];
+    suv[2 * tid + 1] = (double)p2[2 * i + 1];
+  }
+  __syncthreads();
+  opp_epnp_solve(sX, suv, 5, sK, &w, salph, spcs, sperr, tid, 64);
+  const bool ok = w.best > 0 && sdistinct;
+  if (tid < 12 && ok) hyp[(size_t)h * 12 + tid] = w.Rt[w.best][tid];
+  if (tid == 0) valid[h] = ok ? 1 : 0;
+}
+
+// the sequential RANSAC loop over score[0, iters) (opp_ransac_stop), run by thread 0 over the 256ths of the range whose maximum
+// exceeds the current threshold (no other hypothesis can become the best).  Every thread of the 256-thread block calls it.
+// Also returns the lowest-index hypothesis of the highest score (-1 when no hypothesis produced a model).
+__device__ void ransac_scan(const int* __restrict__ score, int iters, int n, int m, double conf, int* s_cmax, int* stop, int* best,
+                            int* best_any) {
+  const int tid = threadIdx.x;
+  const int chunk = (iters + 255) / 256;
+  int mx = -1;
+  for (int i = tid * chunk; i < min(iters, (tid + 1) * chunk); ++i) mx = max(mx, score[i]);
+  s_cmax[tid] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    int niters = iters, bc = 0, b = -1, gmax = -1;
+    for (int c = 0; c < 256; ++c) gmax = max(gmax, s_cmax[c]);
+    for (int c = 0; c < 256; ++c) {
+      const int lo = c * chunk;
+      if (lo >= niters) break;
+      if (s_cmax[c] <= max(bc, m - 1)) continue;
+      for (int i = lo; i < min((c + 1) * chunk, niters); ++i) {
+        const int sc = score[i];
+        if (sc > max(bc, m - 1)) {
+          b = i;
+          bc = sc;
+          if (conf < 1.0) niters = opp_ransac_update_iters(conf, (double)(n - sc) / n, m, niters);
+        }
+      }
+    }
+    *stop = b < 0 ? iters : max(b + 1, niters);
+    *best = b;
+    int ba = -1;
+    if (gmax >= 0)
+      for (int c = 0; c < 256 && ba < 0; ++c)
+        if (s_cmax[c] == gmax)
+          for (int i = c * chunk; i < min(iters, (c + 1) * chunk); ++i)
+            if (score[i] == gmax) {
+              ba = i;
+              break;
+            }
+    *best_any = ba;
+  }
+  __syncthreads();
+}
+
+// P3P under opp_pnp_ransac_ex: the stop index, and the scores with every hypothesis past it masked out (-1) for pnp_refine_kernel
+__global__ __launch_bounds__(256) void pnp_stop_kernel(const int* __restrict__ score, PnpParams prm, int m, double conf,
+                                                       int* __restrict__ score_masked, int* __restrict__ stop_out) {
+  __shared__ int s_cmax[256], s_stop, s_best, s_any;
+  ransac_scan(score, prm.iters, prm.n, m, conf, s_cmax, &s_stop, &s_best, &s_any);
+  for (int h = threadIdx.x; h < prm.iters; h += 256) score_masked[h] = h < s_stop ? score[h] : -1;
+  if (threadIdx.x == 0 && stop_out) *stop_out = s_stop;
+}
+
+// single workgroup, the end of the EPnP path.  mode 0: RANSAC, pose = best hypothesis (n == 4, P3P hypotheses);
+// 1: RANSAC + EPnP refit on the best hypothesis's inliers; 2: one EPnP solve on all n points (n == 5); 3: failure (n < 4).
+// pts: n * 13 doubles of workspace (inlier points, barycentric coordinates, camera points, errors).
+__global__ __launch_bounds__(256) void pnp_epnp_final_kernel(const float* __restrict__ p2, const float* __restrict__ p3, PnpParams prm,
+                                                             const double* __restrict__ hyp, const int* __restrict__ score, int mode, int m,
+                                                             double conf, double* __restrict__ pts, double* __restrict__ pose_out,
+                                                             int* __restrict__ mask, int* __restrict__ n_inl, int* __restrict__ ok_out,
+                                                             int* __restrict__ stop_out) {
+  __shared__ OppEpnpWs w;
+  __shared__ int s_cmax[256], s_off[257];
+  __shared__ int s_stop, s_best, s_any, s_fail, s_hyp, s_nin, s_refit;
+  __shared__ double sK[4];
+  __shared__ OppPose s_pose;
+  const int tid = threadIdx.x, n = prm.n;
+  if (tid < 4) sK[tid] = prm.K4[tid];
+  if (mode <= 1) {
+    ransac_scan(score, prm.iters, n, m, conf, s_cmax, &s_stop, &s_best, &s_any);
+  } else if (tid == 0) {
+    s_stop = 0;
+    s_best = -1;
+    s_any = -1;
+  }
+  if (tid == 0) {
+    s_fail = mode == 3 || (mode <= 1 && s_any < 0);
+    s_hyp = s_best >= 0 ? s_best : s_any;
+    s_refit = mode == 2 || (mode == 1 && s_best >= 0);
+    if (!s_fail && mode <= 1) {
+      for (int k = 0; k < 9; ++k) s_pose.R[k] = hyp[(size_t)s_hyp * 12 + k];
+      for (int k = 0; k < 3; ++k) s_pose.t[k] = hyp[(size_t)s_hyp * 12 + 9 + k];
+    }
+    if (stop_out) *stop_out = s_stop;
+  }
+  __syncthreads();
+  if (s_fail) {   // the reference's cv2.error branch: identity pose, no inliers, state False
+    if (tid < 12) pose_out[tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+    for (int i = tid; i < n; i += 256) mask[i] = 0;
+    if (tid == 0) {
+      *n_inl = 0;
+      *ok_out = 0;
+    }
+    return;
+  }
+  // inliers of the chosen hypothesis (the scoring predicate), compacted in point order: thread t owns points [t*ch, (t+1)*ch)
+  const int ch = (n + 255) / 256, lo = min(n, tid * ch), hi = min(n, lo + ch);
+  const bool all = mode == 2, keep = all || s_best >= 0;   // no hypothesis reached m inliers: pose kept, inliers empty
+  const OppPose P = s_pose;
+  int cnt = 0;
+  for (int i = lo; i < hi; ++i) {
+    bool in = all;
+    if (!all) {
+      const double X[3] = {(double)p3[3 * i] * prm.scale, (double)p3[3 * i + 1] * prm.scale, (double)p3[3 * i + 2] * prm.scale};
+      const double uv[2] = {(double)p2[2 * i], (double)p2[2 * i + 1]};
+      in = keep && opp_reproj_err2(P, prm.K4, X, uv) <= prm.thr2;
+    }
+    mask[i] = in ? 1 : 0;
+    cnt += in ? 1 : 0;
+  }
+  s_off[tid + 1] = cnt;
+  __syncthreads();
+  if (tid == 0) {
+    s_off[0] = 0;
+    for (int t = 0; t < 256; ++t) s_off[t + 1] += s_off[t];
+    s_nin = s_off[256];
+  }
+  __syncthreads();
+  if (s_refit) {
+    const int nin = s_nin;
+    double* X = pts;
+    double* uv = X + (size_t)3 * nin;
+    double* alph = uv + (size_t)2 * nin;
+    double* pcs = alph + (size_t)4 * nin;
+    double* perr = pcs + (size_t)3 * nin;
+    int o = s_off[tid];
+    for (int i = lo; i < hi; ++i)
+      if (mask[i]) {
+        for (int c = 0; c < 3; ++c) X[3 * o + c] = (double)p3[3 * i + c] * prm.scale;
+        uv[2 * o] = (double)p2[2 * i];
+        uv[2 * o + 1] = (double)p2[2 * i + 1];
+        ++o;
+      }
+    __threadfence_block();
+    __syncthreads();
+    opp_epnp_solve(X, uv, nin, sK, &w, alph, pcs, perr, tid, 256);
+    if (tid == 0) {
+      if (w.best > 0) {
+        for (int k = 0; k < 9; ++k) s_pose.R[k] = w.Rt[w.best][k];
+        for (int k = 0; k < 3; ++k) s_pose.t[k] = w.Rt[w.best][9 + k];
+      } else if (mode == 2) {
+        s_fail = 1;
+      }
+    }
+    __syncthreads();
+    if (s_fail) {   // a degenerate 5-point input (OpenCV's solvePnP fails there)
+      if (tid < 12) pose_out[tid] = (tid == 0 || tid == 5 || tid == 10) ? 1.0 : 0.0;
+      for (int i = tid; i < n; i += 256) mask[i] = 0;
+      if (tid == 0) {
+        *n_inl = 0;
+        *ok_out = 0;
+      }
+      return;
+    }
+  }
+  if (tid < 12) {
+    const int r = tid / 4, c = tid % 4;
+    pose_out[tid] = c < 3 ? s_pose.R[r * 3 + c] : s_pose.t[r] / prm.scale;
+  }
+  if (tid == 0) {
+    *n_inl = s_nin;
+    *ok_out = 1;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t opp_pnp_workspace_bytes(int iterations) {
@@ -268,5 +510,69 @@ extern "C" int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_poin
   hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, score, refine_iters, pose_out,
                      inlier_mask, n_inliers, ok);
   OPP_CHECK_LAUNCH("pnp kernels");
+  return OPP_OK;
+}
+
+extern "C" size_t opp_pnp_ex_workspace_bytes(int iterations, int n_points) {
+  if (iterations < 1) iterations = 1;
+  if (n_points < 1) n_points = 1;
+  return opp_align((size_t)iterations * 12 * sizeof(double)) + 3 * opp_align((size_t)iterations * sizeof(int)) +
+         opp_align((size_t)n_points * 13 * sizeof(double)) + 1024;
+}
+
+extern "C" int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, const double* K4, double reproj_error_px,
+                                 double scale, int iterations, unsigned seed, int refine_iters, int solver, double confidence,
+                                 double* pose_out, int* inlier_mask, int* n_inliers, int* ok, int* stop_out, int* samples_out,
+                                 int* scores_out, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  OPP_CHECK_ARG((n_points == 0 || (pts2d && pts3d)) && n_points >= 0 && K4 && pose_out && inlier_mask && n_inliers && ok && ws,
+                "pnp_ex: null argument");
+  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && scale > 0, "pnp_ex: bad parameters");
+  OPP_CHECK_ARG(solver == 0 || solver == 1, "pnp_ex: solver must be 0 (P3P) or 1 (EPnP)");
+  OPP_CHECK_ARG(confidence > 0.0, "pnp_ex: confidence must be > 0 (>= 1: no early stop)");
+  OPP_CHECK_ARG(ws_bytes >= opp_pnp_ex_workspace_bytes(iterations, n_points), "pnp_ex: workspace too small");
+  PnpParams prm;
+  for (int k = 0; k < 4; ++k) prm.K4[k] = K4[k];
+  prm.thr2 = reproj_error_px * reproj_error_px;
+  prm.scale = scale;
+  prm.n = n_points;
+  prm.iters = iterations;
+  prm.seed = seed;
+  char* base = (char*)ws;
+  double* hyp = (double*)base;
+  int* valid = (int*)(base + opp_align((size_t)iterations * 12 * sizeof(double)));
+  int* score = (int*)((char*)valid + opp_align((size_t)iterations * sizeof(int)));
+  int* score2 = (int*)((char*)score + opp_align((size_t)iterations * sizeof(int)));
+  double* pts = (double*)((char*)score2 + opp_align((size_t)iterations * sizeof(int)));
+  const bool sample = solver == 0 ? n_points >= 4 : (n_points == 4 || n_points >= 6);
+  if (sample) {
+    if (solver == 1 && n_points >= 6)
+      hipLaunchKernelGGL(pnp_epnp_hypotheses_kernel, dim3(iterations), dim3(64), 0, stream, pts2d, pts3d, prm, hyp, valid, samples_out);
+    else
+      hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid);
+    hipLaunchKernelGGL(pnp_score_kernel, dim3(opp_cdiv(iterations, 4)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid, score);
+    if (samples_out && !(solver == 1 && n_points >= 6))
+      hipLaunchKernelGGL(pnp_p3p_samples_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, prm, samples_out);
+    if (scores_out && hipMemcpyAsync(scores_out, score, (size_t)iterations * sizeof(int), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
+      opp_set_error("pnp_ex: copy of the scores failed");
+      return OPP_ERR_LAUNCH;
+    }
+  }
+  if (solver == 0) {   // opp_pnp_ransac's launches; the refinement sees only the hypotheses before the stop index
+    if (!sample) {
+      prm.iters = 0;
+      (void)hipMemsetAsync(score, 0, sizeof(int), stream);
+      if (stop_out) (void)hipMemsetAsync(stop_out, 0, sizeof(int), stream);
+    } else {
+      hipLaunchKernelGGL(pnp_stop_kernel, dim3(1), dim3(256), 0, stream, score, prm, 4, confidence, score2, stop_out);
+    }
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, sample ? score2 : score, refine_iters,
+                       pose_out, inlier_mask, n_inliers, ok);
+  } else {
+    const int mode = n_points < 4 ? 3 : (n_points == 4 ? 0 : (n_points == 5 ? 2 : 1));
+    hipLaunchKernelGGL(pnp_epnp_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, score, mode, n_points == 4 ? 4 : 5,
+                       confidence, pts, pose_out, inlier_mask, n_inliers, ok, stop_out);
+  }
+  OPP_CHECK_LAUNCH("pnp_ex kernels");
   return OPP_OK;
 }

@@ -5,8 +5,9 @@
 //   ransac_PnP   /root/reference/src/utils/metric_utils.py:121-204
 //   (cv2.solvePnPRansac(EPNP, 10000 iterations) -> R|t ; accuracy-level parity only: OpenCV's
 //    RANSAC draws from its own RNG)
-// Minimal solver: Grunert's P3P (quartic in the depth ratio, as reviewed by Haralick et al.,
-// IJCV 1994), all arithmetic in double.
+// Minimal solvers: Grunert's P3P (quartic in the depth ratio, as reviewed by Haralick et al.,
+// IJCV 1994) and EPnP (Lepetit et al., IJCV 2009; the reference's own, second half of this file),
+// all arithmetic in double.
 #pragma once
 #include <math.h>
 
@@ -269,4 +270,547 @@ OPP_HD void opp_gn_accumulate(const OppPose& P, const double* K4, const double* 
     for (int c = r; c < 6; ++c) H[r * 6 + c] += Ju[r] * Ju[c] + Jv[r] * Jv[c];
     g[r] -= Ju[r] * ru + Jv[r] * rv;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// EPnP (V. Lepetit, F. Moreno-Noguer, P. Fua, "EPnP: An Accurate O(n) Solution to the PnP Problem", IJCV 81(2), 2009),
+// structured like OpenCV's `epnp` class (the minimal and refit solver of cv2.solvePnPRansac(flags=SOLVEPNP_EPNP)).
+//
+// Written once for the device and the host: every stage takes (tid, nt) -- the calling thread and the number of threads
+// that run it together -- and separates its phases with OPP_BARRIER() (a no-op on the host, where tid = 0, nt = 1).
+// All arrays live in an OppEpnpWs (LDS on the device) or in caller-provided per-point buffers, so the kernels keep no
+// indexed local arrays (no scratch).  Every sum over points runs sequentially in point order, one thread per entry, and
+// FP contraction is off, so a numpy restatement with the same operation order (tests/epnp_reference.py) rounds identically.
+// ---------------------------------------------------------------------------------------------------------------------
+#if defined(__clang__)
+#define OPP_NOFMA _Pragma("clang fp contract(off)")
+#else
+#define OPP_NOFMA
+#endif
+#if defined(__HIPCC__)
+#define OPP_HDI __host__ __device__ __attribute__((always_inline)) inline
+#else
+#define OPP_HDI inline
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+#define OPP_BARRIER() __syncthreads()
+#else
+#define OPP_BARRIER() ((void)0)
+#endif
+
+#define OPP_EPNP_SWEEPS12 10   // cyclic Jacobi sweeps of the 12x12 M^T M (fixed count: deterministic, converged in <= 7)
+#define OPP_EPNP_SWEEPS3 10    // sweeps of the 3x3 solves
+#define OPP_EPNP_GN_ITERS 5    // Gauss-Newton iterations on the betas (OpenCV: 5)
+#define OPP_EPNP_BAD 1e300     // reprojection error of a degenerate candidate
+
+struct OppEpnpWs {
+  double cw[12];              // control points, world frame [4][3]; cw[0..2] = centroid
+  double ax[9];               // principal axes of the world points (rows, descending eigenvalue)
+  double isg[3];              // pseudo-inverse of sqrt(lambda_k / n) (0 for a vanishing axis)
+  double A[2][144], V[2][144];  // Jacobi of M^T M, double-buffered (A -> eigenvalues on the diagonal, V -> eigenvectors)
+  double jd[12], jo[12];      // one parallel Jacobi step: J[i][i] and J[partner(i)][i]
+  int pr[12];                 // partner index of each row / column in the step
+  int ord[12];                // eigenvalues of M^T M, ascending
+  double s3[9], v3[9], t3[9], u3[9];   // 3x3 symmetric eigen-solves (matrix, vectors, double-buffer partners)
+  double L[60], rho[6];       // L_6x10, rho
+  double qa[30], qb[6], qx[5], q1[5], q2[5];   // Householder QR least squares
+  double betas[4][4];         // per candidate 1..3
+  double ccs[12];             // control points, camera frame
+  double pc0[3], abt[9];      // Procrustes
+  double dv[12], sg[3], U[9], Vs[9];   // scratch of the serial stages
+  int o3[3], cols[5];
+  double Rt[4][12];           // per candidate 1..3: R row-major | t
+  double err[4];              // mean reprojection error per candidate
+  int best;                   // chosen candidate, 0 = degenerate
+};
+
+OPP_HDI double opp_dot3_nc(const double* a, const double* b) {
+  OPP_NOFMA
+  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2];
+}
+
+// one symmetric Jacobi rotation (Numerical Recipes convention): J[p][p] = J[q][q] = c, J[p][q] = s, J[q][p] = -s zeroes apq
+OPP_HDI void opp_jacobi_rot(double app, double aqq, double apq, double* c, double* s) {
+  OPP_NOFMA
+  if (apq == 0.0) {
+    *c = 1.0;
+    *s = 0.0;
+    return;
+  }
+  const double th = (aqq - app) / (2.0 * apq);
+  double t = 1.0 / (fabs(th) + sqrt(th * th + 1.0));
+  if (th < 0.0) t = -t;
+  *c = 1.0 / sqrt(t * t + 1.0);
+  *s = t * *c;
+}
+
+// element e of A' = J^T A J and V' = V J for a step of disjoint rotations (pr / jd / jo describe J)
+OPP_HDI void opp_jacobi_elem(const double* A, const double* V, double* A2, double* V2, int N, const int* pr, const double* jd,
+                            const double* jo, int e) {
+  OPP_NOFMA
+  const int i = e / N, j = e % N, pi = pr[i], pj = pr[j];
+  const double bij = jd[i] * A[i * N + j] + jo[i] * A[pi * N + j];
+  const double bipj = jd[i] * A[i * N + pj] + jo[i] * A[pi * N + pj];
+  A2[e] = bij * jd[j] + bipj * jo[j];
+  V2[e] = V[i * N + j] * jd[j] + V[i * N + pj] * jo[j];
+}
+
+// round-robin (circle method) pivot order of the 12x12 solve: step s (0..10), slot k (0..5) -> pair p < q; every pair once per sweep
+OPP_HDI void opp_rr_pair12(int s, int k, int* p, int* q) {
+  int a, b;
+  if (k == 0) {
+    a = 0;
+    b = 1 + s % 11;
+  } else {
+    a = 1 + (s + k) % 11;
+    b = 1 + (s + 11 - k) % 11;
+  }
+  *p = a < b ? a : b;
+  *q = a < b ? b : a;
+}
+
+// sets up the J of one rotation on (p, q) in pr / jd / jo
+OPP_HDI void opp_jacobi_set(const double* A, int N, int p, int q, int* pr, double* jd, double* jo) {
+  double c, s;
+  opp_jacobi_rot(A[p * N + p], A[q * N + q], A[p * N + q], &c, &s);
+  pr[p] = q;
+  pr[q] = p;
+  jd[p] = c;
+  jd[q] = c;
+  jo[p] = -s;
+  jo[q] = s;
+}
+
+// serial cyclic Jacobi of a symmetric 3x3 (pivots (0,1), (0,2), (1,2)); S is destroyed, V receives the eigenvectors (columns),
+// T / U are buffers of 9, pr / jd / jo of 3; on return the eigenvalues are on the diagonal of the returned matrix (S or T)
+OPP_HDI const double* opp_jacobi3(double* S, double* V, double* T, double* U, int* pr, double* jd, double* jo) {
+  for (int k = 0; k < 9; ++k) V[k] = (k % 4 == 0) ? 1.0 : 0.0;
+  double *a = S, *v = V, *a2 = T, *v2 = U;
+  for (int sw = 0; sw < OPP_EPNP_SWEEPS3; ++sw)
+    for (int st = 0; st < 3; ++st) {
+      const int p = st == 2 ? 1 : 0, q = st == 0 ? 1 : 2, r = 3 - p - q;
+      opp_jacobi_set(a, 3, p, q, pr, jd, jo);
+      pr[r] = r;
+      jd[r] = 1.0;
+      jo[r] = 0.0;
+      for (int e = 0; e < 9; ++e) opp_jacobi_elem(a, v, a2, v2, 3, pr, jd, jo, e);
+      double* t = a; a = a2; a2 = t;
+      t = v; v = v2; v2 = t;
+    }
+  if (v != V)
+    for (int k = 0; k < 9; ++k) V[k] = v[k];
+  return a;
+}
+
+// order[0..2] = indices of the diagonal of a 3x3, descending (ties: lower index first)
+OPP_HDI void opp_order3_desc(const double* a, int* o) {
+  o[0] = 0; o[1] = 1; o[2] = 2;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 2 - i; ++j)
+      if (a[o[j + 1] * 4] > a[o[j] * 4]) {
+        const int t = o[j]; o[j] = o[j + 1]; o[j + 1] = t;
+      }
+}
+
+// Householder QR least squares (OpenCV epnp::qr_solve): A [nr][nc] row-major (destroyed), b [nr] (destroyed) -> x [nc].
+// a1 / a2: buffers of nc.  Returns false when A is singular.
+OPP_HDI bool opp_qr_solve(double* A, int nr, int nc, double* b, double* x, double* a1, double* a2) {
+  OPP_NOFMA
+  for (int k = 0; k < nc; ++k) {
+    double eta = fabs(A[k * nc + k]);
+    for (int i = k + 1; i < nr; ++i)
+      if (fabs(A[i * nc + k]) > eta) eta = fabs(A[i * nc + k]);
+    if (!(eta > 0.0)) return false;
+    double sum = 0.0;
+    for (int i = k; i < nr; ++i) {
+      A[i * nc + k] = A[i * nc + k] / eta;
+      sum = sum + A[i * nc + k] * A[i * nc + k];
+    }
+    double sigma = sqrt(sum);
+    if (A[k * nc + k] < 0.0) sigma = -sigma;
+    A[k * nc + k] = A[k * nc + k] + sigma;
+    a1[k] = sigma * A[k * nc + k];
+    a2[k] = -eta * sigma;
+    for (int j = k + 1; j < nc; ++j) {
+      double s = 0.0;
+      for (int i = k; i < nr; ++i) s = s + A[i * nc + k] * A[i * nc + j];
+      const double tau = s / a1[k];
+      for (int i = k; i < nr; ++i) A[i * nc + j] = A[i * nc + j] - tau * A[i * nc + k];
+    }
+  }
+  for (int j = 0; j < nc; ++j) {
+    double tau = 0.0;
+    for (int i = j; i < nr; ++i) tau = tau + A[i * nc + j] * b[i];
+    tau = tau / a1[j];
+    for (int i = j; i < nr; ++i) b[i] = b[i] - tau * A[i * nc + j];
+  }
+  x[nc - 1] = b[nc - 1] / a2[nc - 1];
+  for (int i = nc - 2; i >= 0; --i) {
+    double s = 0.0;
+    for (int j = i + 1; j < nc; ++j) s = s + A[i * nc + j] * x[j];
+    x[i] = (b[i] - s) / a2[i];
+  }
+  return true;
+}
+
+// least squares rho ~ L[:, cols] x  (cols: the columns of L_6x10 used by one beta approximation)
+OPP_HDI bool opp_epnp_ls(OppEpnpWs* w, int nc) {
+  const int* cols = w->cols;
+  for (int i = 0; i < 6; ++i) {
+    for (int j = 0; j < nc; ++j) w->qa[i * nc + j] = w->L[i * 10 + cols[j]];
+    w->qb[i] = w->rho[i];
+  }
+  return opp_qr_solve(w->qa, 6, nc, w->qb, w->qx, w->q1, w->q2);
+}
+
+// Gauss-Newton on the four betas (OpenCV epnp::gauss_newton / compute_A_and_b_gauss_newton)
+OPP_HDI void opp_epnp_gauss_newton(OppEpnpWs* w, double* bt) {
+  OPP_NOFMA
+  for (int it = 0; it < OPP_EPNP_GN_ITERS; ++it) {
+    for (int i = 0; i < 6; ++i) {
+      const double* l = w->L + i * 10;
+      double* a = w->qa + i * 4;
+      a[0] = 2 * l[0] * bt[0] + l[1] * bt[1] + l[3] * bt[2] + l[6] * bt[3];
+      a[1] = l[1] * bt[0] + 2 * l[2] * bt[1] + l[4] * bt[2] + l[7] * bt[3];
+      a[2] = l[3] * bt[0] + l[4] * bt[1] + 2 * l[5] * bt[2] + l[8] * bt[3];
+      a[3] = l[6] * bt[0] + l[7] * bt[1] + l[8] * bt[2] + 2 * l[9] * bt[3];
+      w->qb[i] = w->rho[i] - (l[0] * bt[0] * bt[0] + l[1] * bt[0] * bt[1] + l[2] * bt[1] * bt[1] + l[3] * bt[0] * bt[2] +
+                              l[4] * bt[1] * bt[2] + l[5] * bt[2] * bt[2] + l[6] * bt[0] * bt[3] + l[7] * bt[1] * bt[3] +
+                              l[8] * bt[2] * bt[3] + l[9] * bt[3] * bt[3]);
+    }
+    if (!opp_qr_solve(w->qa, 6, 4, w->qb, w->qx, w->q1, w->q2)) return;
+    for (int k = 0; k < 4; ++k) bt[k] = bt[k] + w->qx[k];
+  }
+}
+
+// eigenvector k (0 = smallest eigenvalue) of M^T M, component m
+#define OPP_EPNP_V(w, vb, k, m) ((vb)[(m) * 12 + (w)->ord[k]])
+
+// L_6x10, rho, the three beta initialisations (approx_1 / 2 / 3) and their Gauss-Newton refinement.  Serial.
+OPP_HDI void opp_epnp_betas(OppEpnpWs* w, const double* vb) {
+  OPP_NOFMA
+  for (int i = 0; i < 6; ++i) {   // control-point pairs (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+    const int pa = i < 3 ? 0 : (i < 5 ? 1 : 2), pb = i < 3 ? i + 1 : (i < 5 ? i - 1 : 3);
+    double* dv = w->dv;
+    for (int k = 0; k < 4; ++k)
+      for (int c = 0; c < 3; ++c) dv[3 * k + c] = OPP_EPNP_V(w, vb, k, 3 * pa + c) - OPP_EPNP_V(w, vb, k, 3 * pb + c);
+    double* r = w->L + i * 10;
+    r[0] = opp_dot3_nc(dv, dv);
+    r[1] = 2 * opp_dot3_nc(dv, dv + 3);
+    r[2] = opp_dot3_nc(dv + 3, dv + 3);
+    r[3] = 2 * opp_dot3_nc(dv, dv + 6);
+    r[4] = 2 * opp_dot3_nc(dv + 3, dv + 6);
+    r[5] = opp_dot3_nc(dv + 6, dv + 6);
+    r[6] = 2 * opp_dot3_nc(dv, dv + 9);
+    r[7] = 2 * opp_dot3_nc(dv + 3, dv + 9);
+    r[8] = 2 * opp_dot3_nc(dv + 6, dv + 9);
+    r[9] = opp_dot3_nc(dv + 9, dv + 9);
+    const double* a = w->cw + 3 * pa;
+    const double* b = w->cw + 3 * pb;
+    w->rho[i] = (a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]);
+  }
+  for (int c = 1; c <= 3; ++c)
+    for (int k = 0; k < 4; ++k) w->betas[c][k] = 0.0;
+  {  // approx_1: B11 B12 B13 B14
+    w->cols[0] = 0; w->cols[1] = 1; w->cols[2] = 3; w->cols[3] = 6;
+    double* bt = w->betas[1];
+    if (opp_epnp_ls(w, 4)) {
+      const double* x = w->qx;
+      if (x[0] < 0) {
+        bt[0] = sqrt(-x[0]);
+        bt[1] = -x[1] / bt[0];
+        bt[2] = -x[2] / bt[0];
+        bt[3] = -x[3] / bt[0];
+      } else {
+        bt[0] = sqrt(x[0]);
+        bt[1] = x[1] / bt[0];
+        bt[2] = x[2] / bt[0];
+        bt[3] = x[3] / bt[0];
+      }
+      opp_epnp_gauss_newton(w, bt);
+    }
+  }
+  {  // approx_2: B11 B12 B22
+    w->cols[0] = 0; w->cols[1] = 1; w->cols[2] = 2;
+    double* bt = w->betas[2];
+    if (opp_epnp_ls(w, 3)) {
+      const double* x = w->qx;
+      if (x[0] < 0) {
+        bt[0] = sqrt(-x[0]);
+        bt[1] = (x[2] < 0) ? sqrt(-x[2]) : 0.0;
+      } else {
+        bt[0] = sqrt(x[0]);
+        bt[1] = (x[2] > 0) ? sqrt(x[2]) : 0.0;
+      }
+      if (x[1] < 0) bt[0] = -bt[0];
+      opp_epnp_gauss_newton(w, bt);
+    }
+  }
+  {  // approx_3: B11 B12 B22 B13 B23
+    for (int k = 0; k < 5; ++k) w->cols[k] = k;
+    double* bt = w->betas[3];
+    if (opp_epnp_ls(w, 5)) {
+      const double* x = w->qx;
+      if (x[0] < 0) {
+        bt[0] = sqrt(-x[0]);
+        bt[1] = (x[2] < 0) ? sqrt(-x[2]) : 0.0;
+      } else {
+        bt[0] = sqrt(x[0]);
+        bt[1] = (x[2] > 0) ? sqrt(x[2]) : 0.0;
+      }
+      if (x[1] < 0) bt[0] = -bt[0];
+      bt[2] = x[3] / bt[0];
+      opp_epnp_gauss_newton(w, bt);
+    }
+  }
+}
+
+// R (row-major) = U V^T from the 3x3 cross-covariance abt (camera x world) via the eigen-solve of abt^T abt; OpenCV's sign fix
+// (negate the last row when det R < 0).  Serial.  Returns false for a rank <= 1 cross-covariance.
+OPP_HDI bool opp_epnp_procrustes(OppEpnpWs* w, double* R) {
+  OPP_NOFMA
+  const double* B = w->abt;
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) w->s3[a * 3 + b] = B[0 * 3 + a] * B[0 * 3 + b] + B[1 * 3 + a] * B[1 * 3 + b] + B[2 * 3 + a] * B[2 * 3 + b];
+  const double* ev = opp_jacobi3(w->s3, w->v3, w->t3, w->u3, w->pr, w->jd, w->jo);
+  int* o = w->o3;
+  opp_order3_desc(ev, o);
+  double *sg = w->sg, *U = w->U, *Vs = w->Vs;
+  for (int k = 0; k < 3; ++k) {
+    const double l = ev[o[k] * 4];
+    sg[k] = l > 0.0 ? sqrt(l) : 0.0;
+    for (int m = 0; m < 3; ++m) Vs[m * 3 + k] = w->v3[m * 3 + o[k]];
+  }
+  if (!(sg[0] > 0.0) || !(sg[1] > 1e-14 * sg[0])) return false;
+  for (int k = 0; k < 3; ++k) {
+    if (k == 2 && !(sg[2] > 1e-12 * sg[0])) break;
+    for (int m = 0; m < 3; ++m) U[m * 3 + k] = (B[m * 3 + 0] * Vs[0 * 3 + k] + B[m * 3 + 1] * Vs[1 * 3 + k] + B[m * 3 + 2] * Vs[2 * 3 + k]) / sg[k];
+  }
+  if (!(sg[2] > 1e-12 * sg[0])) {   // (near-)coplanar camera points: complete the frame
+    U[0 * 3 + 2] = U[1 * 3 + 0] * U[2 * 3 + 1] - U[2 * 3 + 0] * U[1 * 3 + 1];
+    U[1 * 3 + 2] = U[2 * 3 + 0] * U[0 * 3 + 1] - U[0 * 3 + 0] * U[2 * 3 + 1];
+    U[2 * 3 + 2] = U[0 * 3 + 0] * U[1 * 3 + 1] - U[1 * 3 + 0] * U[0 * 3 + 1];
+  }
+  for (int a = 0; a < 3; ++a)
+    for (int b = 0; b < 3; ++b) R[a * 3 + b] = U[a * 3 + 0] * Vs[b * 3 + 0] + U[a * 3 + 1] * Vs[b * 3 + 1] + U[a * 3 + 2] * Vs[b * 3 + 2];
+  const double det = R[0] * R[4] * R[8] + R[1] * R[5] * R[6] + R[2] * R[3] * R[7] - R[2] * R[4] * R[6] - R[1] * R[3] * R[8] -
+                     R[0] * R[5] * R[7];
+  if (det < 0) {
+    R[6] = -R[6];
+    R[7] = -R[7];
+    R[8] = -R[8];
+  }
+  return true;
+}
+
+OPP_HDI bool opp_finite(double x) { return x == x && fabs(x) < 1e300; }
+
+// cyclic Jacobi of w->A[0] (V[0] = I), six disjoint rotations per step (round-robin order), 11 steps per sweep; the buffers
+// alternate every step.  Returns the buffer index holding the result.  Every one of the nt threads calls it.
+OPP_HDI int opp_jacobi12(OppEpnpWs* w, int tid, int nt) {
+  int cur = 0;
+  for (int sw = 0; sw < OPP_EPNP_SWEEPS12; ++sw)
+    for (int st = 0; st < 11; ++st) {
+      for (int k = tid; k < 6; k += nt) {
+        int p, q;
+        opp_rr_pair12(st, k, &p, &q);
+        opp_jacobi_set(w->A[cur], 12, p, q, w->pr, w->jd, w->jo);
+      }
+      OPP_BARRIER();
+      for (int e = tid; e < 144; e += nt) opp_jacobi_elem(w->A[cur], w->V[cur], w->A[cur ^ 1], w->V[cur ^ 1], 12, w->pr, w->jd, w->jo, e);
+      OPP_BARRIER();
+      cur ^= 1;
+    }
+  return cur;
+}
+
+// EPnP on n >= 4 correspondences.  X [n][3] world points (already scaled), uv [n][2] pixels, K4 = fx, fy, cx, cy.
+// alph [n][4], pcs [n][3], perr [n]: per-point buffers.  Every one of the nt threads calls it (it contains barriers).
+// On return (all threads) w->best > 0 and w->Rt[w->best] holds the pose, or w->best == 0 for a degenerate input.
+OPP_HDI void opp_epnp_solve(const double* X, const double* uv, int n, const double* K4, OppEpnpWs* w, double* alph, double* pcs,
+                           double* perr, int tid, int nt) {
+  OPP_NOFMA
+  // centroid and scatter matrix of the world points (sequential in point order, one thread per entry)
+  for (int e = tid; e < 3; e += nt) {
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s = s + X[3 * i + e];
+    w->cw[e] = s / n;
+  }
+  OPP_BARRIER();
+  for (int e = tid; e < 6; e += nt) {
+    const int a = e < 3 ? 0 : (e < 5 ? 1 : 2), b = e < 3 ? e : (e < 5 ? e - 2 : 2);
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) s = s + (X[3 * i + a] - w->cw[a]) * (X[3 * i + b] - w->cw[b]);
+    w->s3[a * 3 + b] = s;
+    w->s3[b * 3 + a] = s;
+  }
+  OPP_BARRIER();
+  // control points: centroid + sqrt(lambda_k / n) e_k along the principal axes; pseudo-inverse of their offsets
+  if (tid == 0) {
+    const double* ev = opp_jacobi3(w->s3, w->v3, w->t3, w->u3, w->pr, w->jd, w->jo);
+    int* o = w->o3;
+    opp_order3_desc(ev, o);
+    double* sg = w->sg;
+    for (int k = 0; k < 3; ++k) {
+      const double l = ev[o[k] * 4];
+      sg[k] = l > 0.0 ? sqrt(l / n) : 0.0;
+    }
+    for (int k = 0; k < 3; ++k) {
+      w->isg[k] = (sg[k] > 1e-12 * sg[0] && sg[k] > 0.0) ? 1.0 / sg[k] : 0.0;
+      for (int c = 0; c < 3; ++c) {
+        w->ax[k * 3 + c] = w->v3[c * 3 + o[k]];
+        w->cw[3 * (k + 1) + c] = w->cw[c] + sg[k] * w->ax[k * 3 + c];
+      }
+    }
+  }
+  OPP_BARRIER();
+  // barycentric coordinates
+  for (int i = tid; i < n; i += nt) {
+    const double d0 = X[3 * i] - w->cw[0], d1 = X[3 * i + 1] - w->cw[1], d2 = X[3 * i + 2] - w->cw[2];
+    const double a0 = (w->ax[0] * d0 + w->ax[1] * d1 + w->ax[2] * d2) * w->isg[0];
+    const double a1 = (w->ax[3] * d0 + w->ax[4] * d1 + w->ax[5] * d2) * w->isg[1];
+    const double a2 = (w->ax[6] * d0 + w->ax[7] * d1 + w->ax[8] * d2) * w->isg[2];
+    alph[4 * i + 0] = 1.0 - a0 - a1 - a2;
+    alph[4 * i + 1] = a0;
+    alph[4 * i + 2] = a1;
+    alph[4 * i + 3] = a2;
+  }
+  OPP_BARRIER();
+  // M^T M: upper triangle, one thread per entry, rows of M in point order (u row, then v row)
+  for (int e = tid; e < 78; e += nt) {
+    int r = 0, f = e;
+    while (f >= 12 - r) {
+      f -= 12 - r;
+      ++r;
+    }
+    const int c = r + f;
+    const int jr = r / 3, kr = r % 3, jc = c / 3, kc = c % 3;
+    double s = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const double ar = alph[4 * i + jr], ac = alph[4 * i + jc];
+      const double du = K4[2] - uv[2 * i], dv = K4[3] - uv[2 * i + 1];
+      const double mur = kr == 0 ? ar * K4[0] : (kr == 1 ? 0.0 : ar * du);
+      const double muc = kc == 0 ? ac * K4[0] : (kc == 1 ? 0.0 : ac * du);
+      const double mvr = kr == 0 ? 0.0 : (kr == 1 ? ar * K4[1] : ar * dv);
+      const double mvc = kc == 0 ? 0.0 : (kc == 1 ? ac * K4[1] : ac * dv);
+      s = s + mur * muc;
+      s = s + mvr * mvc;
+    }
+    w->A[0][r * 12 + c] = s;
+    w->A[0][c * 12 + r] = s;
+    w->V[0][r * 12 + c] = r == c ? 1.0 : 0.0;
+    w->V[0][c * 12 + r] = r == c ? 1.0 : 0.0;
+  }
+  OPP_BARRIER();
+  const int cur = opp_jacobi12(w, tid, nt);
+  const double* vb = w->V[cur];
+  if (tid == 0) {
+    for (int k = 0; k < 12; ++k) w->ord[k] = k;   // ascending eigenvalues, ties: lower index first
+    for (int i = 0; i < 12; ++i)
+      for (int j = 0; j < 11 - i; ++j)
+        if (w->A[cur][w->ord[j + 1] * 13] < w->A[cur][w->ord[j] * 13]) {
+          const int t = w->ord[j]; w->ord[j] = w->ord[j + 1]; w->ord[j + 1] = t;
+        }
+    opp_epnp_betas(w, vb);
+  }
+  OPP_BARRIER();
+  for (int cand = 1; cand <= 3; ++cand) {
+    if (tid == 0) {   // control points in the camera frame
+      for (int m = 0; m < 12; ++m) {
+        const double* bt = w->betas[cand];
+        w->ccs[m] = bt[0] * OPP_EPNP_V(w, vb, 0, m) + bt[1] * OPP_EPNP_V(w, vb, 1, m) + bt[2] * OPP_EPNP_V(w, vb, 2, m) +
+                    bt[3] * OPP_EPNP_V(w, vb, 3, m);
+      }
+    }
+    OPP_BARRIER();
+    for (int i = tid; i < n; i += nt)
+      for (int c = 0; c < 3; ++c)
+        pcs[3 * i + c] = alph[4 * i] * w->ccs[c] + alph[4 * i + 1] * w->ccs[3 + c] + alph[4 * i + 2] * w->ccs[6 + c] +
+                         alph[4 * i + 3] * w->ccs[9 + c];
+    OPP_BARRIER();
+    const double sgn = pcs[2] < 0.0 ? -1.0 : 1.0;   // solve_for_sign: the first point in front of the camera
+    for (int e = tid; e < 3; e += nt) {
+      double s = 0.0;
+      for (int i = 0; i < n; ++i) s = s + sgn * pcs[3 * i + e];
+      w->pc0[e] = s / n;
+    }
+    OPP_BARRIER();
+    for (int e = tid; e < 9; e += nt) {
+      const int a = e / 3, b = e % 3;
+      double s = 0.0;
+      for (int i = 0; i < n; ++i) s = s + (sgn * pcs[3 * i + a] - w->pc0[a]) * (X[3 * i + b] - w->cw[b]);
+      w->abt[e] = s;
+    }
+    OPP_BARRIER();
+    if (tid == 0) {
+      double* P = w->Rt[cand];
+      const bool ok = opp_epnp_procrustes(w, P);
+      for (int a = 0; a < 3; ++a) P[9 + a] = w->pc0[a] - (P[a * 3] * w->cw[0] + P[a * 3 + 1] * w->cw[1] + P[a * 3 + 2] * w->cw[2]);
+      w->err[cand] = ok ? 0.0 : OPP_EPNP_BAD;
+    }
+    OPP_BARRIER();
+    for (int i = tid; i < n; i += nt) {
+      const double* P = w->Rt[cand];
+      const double* x = X + 3 * i;
+      const double xc = P[0] * x[0] + P[1] * x[1] + P[2] * x[2] + P[9];
+      const double yc = P[3] * x[0] + P[4] * x[1] + P[5] * x[2] + P[10];
+      const double zc = P[6] * x[0] + P[7] * x[1] + P[8] * x[2] + P[11];
+      const double iz = 1.0 / zc;
+      const double ue = K4[2] + K4[0] * xc * iz, ve = K4[3] + K4[1] * yc * iz;
+      perr[i] = sqrt((uv[2 * i] - ue) * (uv[2 * i] - ue) + (uv[2 * i + 1] - ve) * (uv[2 * i + 1] - ve));
+    }
+    OPP_BARRIER();
+    if (tid == 0) {
+      double s = 0.0;
+      for (int i = 0; i < n; ++i) s = s + perr[i];
+      s = s / n;
+      bool fin = opp_finite(s);
+      for (int k = 0; k < 12; ++k) fin = fin && opp_finite(w->Rt[cand][k]);
+      if (w->err[cand] == 0.0) w->err[cand] = fin ? s : OPP_EPNP_BAD;
+    }
+    OPP_BARRIER();
+  }
+  if (tid == 0) {
+    int N = 1;
+    if (w->err[2] < w->err[1]) N = 2;
+    if (w->err[3] < w->err[N]) N = 3;
+    w->best = w->err[N] < OPP_EPNP_BAD ? N : 0;
+  }
+  OPP_BARRIER();
+}
+
+// OpenCV's RANSACUpdateNumIters (repeated multiplication in place of std::pow)
+OPP_HDI int opp_ransac_update_iters(double p, double ep, int m, int max_iters) {
+  OPP_NOFMA
+  p = fmax(p, 0.0);
+  p = fmin(p, 1.0);
+  ep = fmax(ep, 0.0);
+  ep = fmin(ep, 1.0);
+  double num = 1.0 - p;
+  if (num < 2.2250738585072014e-308) num = 2.2250738585072014e-308;
+  const double q = 1.0 - ep;
+  double qm = 1.0;
+  for (int k = 0; k < m; ++k) qm = qm * q;
+  double denom = 1.0 - qm;
+  if (denom < 2.2250738585072014e-308) return 0;
+  num = log(num);
+  denom = log(denom);
+  return (denom >= 0 || -num >= max_iters * (-denom)) ? max_iters : (int)rint(num / denom);
+}
+
+// the sequential RANSAC loop over per-hypothesis inlier counts (score < 0: no model): a hypothesis becomes the best when its
+// count > max(best count, m - 1); after each new best niters = update(...) unless confidence >= 1.  Returns the number of
+// hypotheses the loop evaluates (the stop index); *best = the best hypothesis, -1 if none qualified.
+OPP_HDI int opp_ransac_stop(const int* score, int iters, int n, int m, double confidence, int* best) {
+  int niters = iters, bc = 0, b = -1, it = 0;
+  for (; it < niters; ++it) {
+    const int s = score[it];
+    if (s > (bc > m - 1 ? bc : m - 1)) {
+      b = it;
+      bc = s;
+      if (confidence < 1.0) niters = opp_ransac_update_iters(confidence, (double)(n - s) / n, m, niters);
+    }
+  }
+  *best = b;
+  return it;
 }
