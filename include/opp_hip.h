@@ -331,8 +331,9 @@ int opp_linear_attention_train_backward(const float* q, const float* k, const fl
  * ResNetFPN_8_2.forward (backbone/resnet.py:141-164): nn.Conv2d (no bias), nn.BatchNorm2d in train(), ReLU / LeakyReLU(0.01),
  * the residual adds and the two bilinear x2 upsamples.  opp_backbone_train_tape is opp_backbone_train writing every tensor the
  * backward needs (raw convolution outputs, block outputs, batch mean / 1/sqrt(var + eps) per BatchNorm) into the caller's
- * `tape` (nothing is recomputed later); opp_backbone_backward takes the gradients of the two outputs, feat_c [B][H/8][W/8][256]
- * and feat_f [B][H/2][W/2][128] (NHWC), and writes the gradient of EVERY backbone parameter: `weights` is the table given to
+ * `tape` (nothing is recomputed later) -- one walk serves both (csrc/api.hip: backbone_train_walk; the two entries differ in
+ * where it writes: a slot of the tape each, or the reused maps of the workspace); opp_backbone_backward takes the gradients of
+ * the two outputs, feat_c [B][H/8][W/8][256] and feat_f [B][H/2][W/2][128] (NHWC), and writes the gradient of EVERY backbone parameter: `weights` is the table given to
  * opp_pack_weights (the raw convolution weights are read from it), grads[i] the device pointer that receives the gradient of
  * weights[i] in the PyTorch layout ([cout][cin][kh][kw]; BatchNorm weight / bias [C]); entries of tensors outside the backbone
  * and of the running statistics are ignored and may be NULL.  Convolution input gradients run on the implicit-GEMM kernel with

@@ -650,42 +650,56 @@ bool conv_takes_split(const ConvDesc& d, int prec) {
 }
 inline size_t split_row_bytes(int c_pad) { return (size_t)c_pad * 6; }
 
+// output extent of a convolution along one axis; pad < 0: the "same" padding ks / 2
+inline int conv_out(int in, int ks, int stride, int pad = -1) { return (in + 2 * (pad < 0 ? ks / 2 : pad) - ks) / stride + 1; }
+
+// what a run_conv call may ask for beyond the plain single-image "same" convolution with folded weights; call sites name what they set
+// ({.Bn = B, .raw = true}: designated initializers, which hipcc accepts under -std=c++17; members in declaration order)
+struct ConvOpts {
+  int tile_cfg = -1;             // >= 0: this tile configuration instead of the launcher's own choice (tests / tools)
+  int Bn = 1;                    // images (or patches) in the batch
+  bool raw = false;              // training mode: unfolded weights, no BatchNorm shift (bn_train applies the batch statistics afterwards)
+  int pad = -1;                  // < 0: ks / 2
+  int splitk_force = -1;         // OppGemm::splitk_force
+  const void* x3 = nullptr;      // pre-split twin of the input
+  void* y3 = nullptr;            // pre-split rows of the output are written here
+};
+
 int run_conv(const float* x, int Hin, int Win, const ConvDesc& d, int stride, const float* res, int res_mode, int act,
-             float* y, hipStream_t s, int h2, int tile_cfg = -1, int Bn = 1, bool raw = false, int pad = -1, int splitk_force = -1,
-             const void* x3 = nullptr, void* y3 = nullptr) {
+             float* y, hipStream_t s, int h2, const ConvOpts& o = ConvOpts()) {
   OppGemm g;
-  const bool a_split = x3 != nullptr && !raw && conv_takes_split(d, h2);
+  const bool raw = o.raw;
+  const bool a_split = o.x3 != nullptr && !raw && conv_takes_split(d, h2);
   OPP_CHECK_ARG(a_split || x != nullptr, "conv: no fp32 input for a convolution that cannot take the pre-split one");
-  OPP_CHECK_ARG(y3 == nullptr || h2 == OPP_PREC_BF16X3, "conv: pre-split output is a bf16x3 feature");
+  OPP_CHECK_ARG(o.y3 == nullptr || h2 == OPP_PREC_BF16X3, "conv: pre-split output is a bf16x3 feature");
   static const bool splitk_on = !(getenv("OPP_CONV_SPLITK") && getenv("OPP_CONV_SPLITK")[0] == '0');   // A/B switch of the tools
   g.splitk_ws = splitk_on ? t_splitk_ws : nullptr;
   g.splitk_ws_floats = g.splitk_ws ? t_splitk_ws_floats : 0;
-  g.splitk_force = splitk_force;
+  g.splitk_force = o.splitk_force;
   g.nonfinite = t_status_flag;
   g.tile_policy = t_tile_policy;
   g.conv = 1;
   g.prec = h2;
-  // raw = training mode: unfolded weights, no BatchNorm shift (bn_train applies the batch statistics afterwards)
   const float* h2s = raw ? d.h2s_train : d.h2s;
   g.h2_inv = (h2 == OPP_PREC_FP16X2 && h2s) ? h2s + 1 : nullptr;
-  g.A0 = a_split ? static_cast<const float*>(x3) : x;
+  g.A0 = a_split ? static_cast<const float*>(o.x3) : x;
   g.a_split = a_split ? 1 : 0;
-  g.C3 = y3;
+  g.C3 = o.y3;
   g.ld3 = (int)split_row_bytes(d.cout_pad());
-  g.Bn = Bn;
+  g.Bn = o.Bn;
   g.Hin = Hin;
   g.Win = Win;
   g.Cin = d.cin_pad();
   g.ksize = d.ks;
   g.stride = stride;
-  g.pad = pad < 0 ? d.ks / 2 : pad;
-  g.Hout = (Hin + 2 * g.pad - d.ks) / stride + 1;
-  g.Wout = (Win + 2 * g.pad - d.ks) / stride + 1;
+  g.pad = o.pad < 0 ? d.ks / 2 : o.pad;
+  g.Hout = conv_out(Hin, d.ks, stride, g.pad);
+  g.Wout = conv_out(Win, d.ks, stride, g.pad);
   g.W = raw ? d.w_train : d.w;
   g.K = d.k_len();
   g.tail_grp = opp_conv_tail_grp(d.cin, d.ks);
   g.ldw = (int)split_floats((size_t)g.K, h2);
-  g.M = Bn * g.Hout * g.Wout;
+  g.M = o.Bn * g.Hout * g.Wout;
   g.N = d.cout_pad();
   g.C = y;
   g.ldc = d.cout_pad();
@@ -707,35 +721,40 @@ int run_conv(const float* x, int Hin, int Win, const ConvDesc& d, int stride, co
   // 196-channel layers (bf16x3): 192 columns on the MFMA kernel -- no padded sub-tile -- and the last 4 (+ the zero padding channels of
   // the 224-channel row) on the vector ALU.  Shape-only decision: every tile policy, batch size and the match-driven patches take it.
   const float* wt = raw ? d.w_tail_train : d.w_tail;
-  if (t_conv_tail && h2 == OPP_PREC_BF16X3 && wt != nullptr && tile_cfg < 0) {
+  if (t_conv_tail && h2 == OPP_PREC_BF16X3 && wt != nullptr && o.tile_cfg < 0) {
     OppGemm body = g;
     body.N = d.body_cols();
     body.n_store = d.body_cols();
     body.alg_flops = 2.0 * (double)g.M * (double)d.body_cols() * (double)(d.ks * d.ks * d.cin);
-    OPP_TRY(opp_gemm_launch_cfg(body, tile_cfg, s));
+    OPP_TRY(opp_gemm_launch_cfg(body, o.tile_cfg, s));
     return opp_conv_tail(g, wt, d.body_cols(), d.tail_cols(), s);
   }
-  return opp_gemm_launch_cfg(g, tile_cfg, s);
+  return opp_gemm_launch_cfg(g, o.tile_cfg, s);
 }
 
+// the pre-split twins of a block's x / tmp / y (null = not kept)
+struct BlockTwins {
+  const void* x3 = nullptr;
+  void *tmp3 = nullptr, *y3 = nullptr;
+};
+
 // BasicBlock.forward (resnet.py:37-45)
-// x3 / tmp3 / y3: the pre-split twins of x / tmp / y (null = not kept).  A map is written in fp32 only where something reads it in fp32
-// (a shortcut, a convolution with a packed K tail, the caller): y = null with y3 set drops the fp32 copy, and tmp is fp32 only when conv2
-// cannot take the split rows.
+// A map is written in fp32 only where something reads it in fp32 (a shortcut, a convolution with a packed K tail, the caller): y = null
+// with tw.y3 set drops the fp32 copy, and tmp is fp32 only when conv2 cannot take the split rows.
 int run_block(const float* x, int Hin, int Win, const BlockDesc& b, int stride, float* tmp, float* ds, float* y,
-              hipStream_t s, int h2, const void* x3 = nullptr, void* tmp3 = nullptr, void* y3 = nullptr) {
+              hipStream_t s, int h2, const BlockTwins& tw = BlockTwins()) {
   const int Ho = Hin / stride, Wo = Win / stride;
-  const bool t_split = tmp3 != nullptr && conv_takes_split(b.conv2, h2);
-  OPP_TRY(run_conv(x, Hin, Win, b.conv1, stride, nullptr, OPP_RES_NONE, OPP_ACT_RELU, t_split ? nullptr : tmp, s, h2, -1, 1, false, -1, -1, x3,
-                   t_split ? tmp3 : nullptr));
+  const bool t_split = tw.tmp3 != nullptr && conv_takes_split(b.conv2, h2);
+  OPP_TRY(run_conv(x, Hin, Win, b.conv1, stride, nullptr, OPP_RES_NONE, OPP_ACT_RELU, t_split ? nullptr : tmp, s, h2,
+                   {.x3 = tw.x3, .y3 = t_split ? tw.tmp3 : nullptr}));
   const float* shortcut = x;
   if (b.has_down) {
-    OPP_TRY(run_conv(x, Hin, Win, b.down, stride, nullptr, OPP_RES_NONE, OPP_ACT_NONE, ds, s, h2, -1, 1, false, -1, -1, x3));
+    OPP_TRY(run_conv(x, Hin, Win, b.down, stride, nullptr, OPP_RES_NONE, OPP_ACT_NONE, ds, s, h2, {.x3 = tw.x3}));
     shortcut = ds;
   }
   OPP_CHECK_ARG(shortcut != nullptr, "block: the shortcut needs the fp32 input map");
-  return run_conv(t_split ? nullptr : tmp, Ho, Wo, b.conv2, 1, shortcut, OPP_RES_DIRECT, OPP_ACT_RELU, y, s, h2, -1, 1, false, -1, -1,
-                  t_split ? tmp3 : nullptr, y3);
+  return run_conv(t_split ? nullptr : tmp, Ho, Wo, b.conv2, 1, shortcut, OPP_RES_DIRECT, OPP_ACT_RELU, y, s, h2,
+                  {.x3 = t_split ? tw.tmp3 : nullptr, .y3 = tw.y3});
 }
 
 struct BackboneBufs {
@@ -746,8 +765,9 @@ struct BackboneBufs {
        *u2s = nullptr;
 };
 
-size_t plan_backbone(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b) {
-  const size_t p2 = (size_t)(H / 2) * (W / 2), p4 = (size_t)(H / 4) * (W / 4), p8 = (size_t)(H / 8) * (W / 8);
+// the maps of ResNetFPN_8_2.forward over B images.  infer (the eval-mode walk, B = 1) adds the split-K scratch and the pre-split twins
+size_t plan_backbone(const opp_ctx* c, int B, int H, int W, bool infer, Arena& a, BackboneBufs& b) {
+  const size_t p2 = (size_t)B * (H / 2) * (W / 2), p4 = (size_t)B * (H / 4) * (W / 4), p8 = (size_t)B * (H / 8) * (W / 8);
   const int c1 = pad32(c->cfg.block_dims[0]), c2 = pad32(c->cfg.block_dims[1]), c3 = pad32(c->cfg.block_dims[2]);
   b.col = a.f(p2 * 64);
   b.x0 = a.f(p2 * c1);
@@ -767,6 +787,7 @@ size_t plan_backbone(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b) 
   b.x2o = a.f(p4 * c2);
   b.l1 = a.f(p2 * c2);
   b.u1 = a.f(p2 * c2);
+  if (!infer) return a.off;
   b.sk1 = a.f(kSplitKScratchFloats);
   b.sk2 = a.f(kSplitKScratchFloats);
   if (gemm_prec(c->cfg) == OPP_PREC_BF16X3 && asp_env_on()) {
@@ -784,6 +805,33 @@ size_t plan_backbone(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b) 
   return a.off;
 }
 
+// The stem as a GEMM over its im2col rows (opp_stem_im2col: [M][64], 49 taps + zero padding): C [M][pad32(cout)] = act(col * w^T + bias).
+// w / h2s: the folded packing with the BatchNorm shift as bias (eval), or the raw one and no bias (training: bn_train follows).
+// nonfinite and h2_inv are read by the fp16x2 instances only (gemm_mfma.hip, epilogue): inert in fp32 / bf16x3, the arithmetics the
+// training step accepts.
+OppGemm stem_gemm(const opp_ctx* c, const float* col, int M, const float* w, const float* h2s, const float* bias, int act, float* y) {
+  const int hp = gemm_prec(c->cfg);
+  OppGemm g;
+  g.nonfinite = t_status_flag;
+  g.tile_policy = t_tile_policy;
+  g.A0 = col;
+  g.lda0 = 64;
+  g.ksplit = 64;
+  g.W = w;
+  g.ldw = (int)split_floats(64, hp);
+  g.M = M;
+  g.N = c->stem.cout;
+  g.K = 64;
+  g.C = y;
+  g.ldc = pad32(c->stem.cout);
+  g.n_store = pad32(c->stem.cout);
+  g.bias = bias;
+  g.act = act;
+  g.prec = hp;
+  g.h2_inv = hp == OPP_PREC_FP16X2 ? h2s + 1 : nullptr;
+  return g;
+}
+
 // phase 0: the whole ResNetFPN_8_2.forward; 1: stem .. layer3 + layer3_outconv (-> feat_c, the coarse map);
 // 2: the FPN fine branch (-> feat_f), which needs only x1, x2 and feat_c of phase 1 -- the coarse level does not depend on it;
 // 3: the 1/4-resolution half of that branch only (-> x2_out); 4: its 1/2-resolution half (x1, x2_out -> feat_f; bufs prepared by the caller).
@@ -797,7 +845,7 @@ int backbone_impl(opp_ctx* c, const float* image, int H, int W, float* feat_c, f
   BackboneBufs local;
   BackboneBufs& b = bufs ? *bufs : local;
   if (phase == 0 || phase == 1) {
-    plan_backbone(c, H, W, a, b);
+    plan_backbone(c, 1, H, W, true, a, b);
     if (!a.ok) {
       opp_set_error("backbone: workspace too small");
       return OPP_ERR_WORKSPACE;
@@ -832,57 +880,39 @@ int backbone_impl(opp_ctx* c, const float* image, int H, int W, float* feat_c, f
       OPP_TRY(opp_stem_direct(image, H, W, c->stem.w, c->stem.bias, b.x0, pad32(c->stem.cout), s, x0s, (int)split_row_bytes(pad32(c->stem.cout))));
     } else {
       OPP_TRY(opp_stem_im2col(image, 1, H, W, b.col, s));
-      OppGemm g;
-      g.nonfinite = t_status_flag;
-      g.tile_policy = t_tile_policy;
-      g.A0 = b.col;
-      g.lda0 = 64;
-      g.ksplit = 64;
-      g.W = c->stem.w;
-      g.ldw = (int)split_floats(64, hp);
-      g.M = H2 * W2;
-      g.N = c->stem.cout;
-      g.K = 64;
-      g.C = b.x0;
-      g.ldc = pad32(c->stem.cout);
-      g.n_store = pad32(c->stem.cout);
-      g.bias = c->stem.bias;
-      g.act = OPP_ACT_RELU;
-      g.prec = hp;
-      g.h2_inv = hp == OPP_PREC_FP16X2 ? c->stem.h2s + 1 : nullptr;
-      OPP_TRY(opp_gemm_launch(g, s));
+      OPP_TRY(opp_gemm_launch(stem_gemm(c, b.col, H2 * W2, c->stem.w, c->stem.h2s, c->stem.bias, OPP_ACT_RELU, b.x0), s));
     }
     // (x0, x1a, x3a are shortcuts and x1 / x2 may leave through x1_ext / feed a convolution with a packed K tail: those keep their fp32 copy)
     void* x1as = twin(b.x1as, {&B[1].conv1});
-    OPP_TRY(run_block(b.x0, H2, W2, B[0], 1, b.t1, nullptr, b.x1a, s, hp, x0s, b.t1s, x1as));   // layer1 (:144)
+    OPP_TRY(run_block(b.x0, H2, W2, B[0], 1, b.t1, nullptr, b.x1a, s, hp, {.x3 = x0s, .tmp3 = b.t1s, .y3 = x1as}));   // layer1 (:144)
     b.x1s = twin(b.x1s, {&B[2].conv1, &B[2].down, &c->l1_out});
-    OPP_TRY(run_block(b.x1a, H2, W2, B[1], 1, b.t1, nullptr, b.x1, s, hp, x1as, b.t1s, b.x1s));
-    OPP_TRY(run_block(b.x1, H2, W2, B[2], 2, b.t2, b.ds2, b.x2a, s, hp, b.x1s));                // layer2 (:145)
+    OPP_TRY(run_block(b.x1a, H2, W2, B[1], 1, b.t1, nullptr, b.x1, s, hp, {.x3 = x1as, .tmp3 = b.t1s, .y3 = b.x1s}));
+    OPP_TRY(run_block(b.x1, H2, W2, B[2], 2, b.t2, b.ds2, b.x2a, s, hp, {.x3 = b.x1s}));                              // layer2 (:145)
     b.x2s = twin(b.x2s, {&B[4].conv1, &B[4].down, &c->l2_out});
-    OPP_TRY(run_block(b.x2a, H4, W4, B[3], 1, b.t2, nullptr, b.x2, s, hp, nullptr, nullptr, b.x2s));
+    OPP_TRY(run_block(b.x2a, H4, W4, B[3], 1, b.t2, nullptr, b.x2, s, hp, {.y3 = b.x2s}));
     void* x3as = twin(b.x3as, {&B[5].conv1});
-    OPP_TRY(run_block(b.x2, H4, W4, B[4], 2, b.t3, b.ds3, b.x3a, s, hp, b.x2s, b.t3s, x3as));   // layer3 (:146)
+    OPP_TRY(run_block(b.x2, H4, W4, B[4], 2, b.t3, b.ds3, b.x3a, s, hp, {.x3 = b.x2s, .tmp3 = b.t3s, .y3 = x3as}));   // layer3 (:146)
     void* x3s = twin(b.x3s, {&c->l3_out});
     float* x3f = fp32_of(b.x3, x3s, {&c->l3_out});
-    OPP_TRY(run_block(b.x3a, H8, W8, B[5], 1, b.t3, nullptr, x3f, s, hp, x3as, b.t3s, x3s));
+    OPP_TRY(run_block(b.x3a, H8, W8, B[5], 1, b.t3, nullptr, x3f, s, hp, {.x3 = x3as, .tmp3 = b.t3s, .y3 = x3s}));
     // FPN (:149-157)
-    OPP_TRY(run_conv(x3f, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, -1, 1, false, -1, -1, x3s));
+    OPP_TRY(run_conv(x3f, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, {.x3 = x3s}));
   }
   if (phase == 0 || phase == 2 || phase == 3) {
     SplitKScope sk_scope(b.sk2);
     void* l2s = twin(b.l2s, {&c->l2_out2a});
     float* l2f = fp32_of(b.l2, l2s, {&c->l2_out2a});
-    OPP_TRY(run_conv(b.x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, l2f, s, hp, -1, 1, false, -1, -1, b.x2s, l2s));
+    OPP_TRY(run_conv(b.x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, l2f, s, hp, {.x3 = b.x2s, .y3 = l2s}));
     void* u2s = twin(b.u2s, {&c->l2_out2b});
     float* u2f = fp32_of(b.u2, u2s, {&c->l2_out2b});
-    OPP_TRY(run_conv(l2f, H4, W4, c->l2_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, u2f, s, hp, -1, 1, false, -1, -1, l2s, u2s));
-    OPP_TRY(run_conv(u2f, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.x2o, s, hp, -1, 1, false, -1, -1, u2s));
+    OPP_TRY(run_conv(l2f, H4, W4, c->l2_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, u2f, s, hp, {.x3 = l2s, .y3 = u2s}));
+    OPP_TRY(run_conv(u2f, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.x2o, s, hp, {.x3 = u2s}));
   }
   if (phase == 0 || phase == 2 || phase == 4) {
     SplitKScope sk_scope(b.sk2);
     static const int l1out_cfg = getenv("OPP_L1OUT_CFG") ? atoi(getenv("OPP_L1OUT_CFG")) : -1;   // A/B switch (tools): tile of the K = 128 lateral
-    OPP_TRY(run_conv(b.x1, H2, W2, c->l1_out, 1, b.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l1, s, hp, hp == OPP_PREC_BF16X3 ? l1out_cfg : -1, 1, false,
-                     -1, -1, b.x1s));
+    OPP_TRY(run_conv(b.x1, H2, W2, c->l1_out, 1, b.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l1, s, hp,
+                     {.tile_cfg = hp == OPP_PREC_BF16X3 ? l1out_cfg : -1, .x3 = b.x1s}));
     OPP_TRY(run_conv(b.l1, H2, W2, c->l1_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, b.u1, s, hp));
     OPP_TRY(run_conv(b.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp));
   }
@@ -891,129 +921,9 @@ int backbone_impl(opp_ctx* c, const float* image, int H, int W, float* feat_c, f
 
 }  // namespace
 
-namespace {
-
-// ---- training mode: ResNetFPN_8_2.forward with BatchNorm batch statistics, B images per call ----------------
-size_t plan_backbone_train(const opp_ctx* c, int B, int H, int W, Arena& a, BackboneBufs& b, float** raw, void** bn_scratch) {
-  const size_t p2 = (size_t)B * (H / 2) * (W / 2), p4 = (size_t)B * (H / 4) * (W / 4), p8 = (size_t)B * (H / 8) * (W / 8);
-  const int c1 = pad32(c->cfg.block_dims[0]), c2 = pad32(c->cfg.block_dims[1]), c3 = pad32(c->cfg.block_dims[2]);
-  b.col = a.f(p2 * 64);
-  b.x0 = a.f(p2 * c1);
-  b.t1 = a.f(p2 * c1);
-  b.x1a = a.f(p2 * c1);
-  b.x1 = a.f(p2 * c1);
-  b.t2 = a.f(p4 * c2);
-  b.ds2 = a.f(p4 * c2);
-  b.x2a = a.f(p4 * c2);
-  b.x2 = a.f(p4 * c2);
-  b.t3 = a.f(p8 * c3);
-  b.ds3 = a.f(p8 * c3);
-  b.x3a = a.f(p8 * c3);
-  b.x3 = a.f(p8 * c3);
-  b.l2 = a.f(p4 * c3);
-  b.u2 = a.f(p4 * c3);
-  b.x2o = a.f(p4 * c2);
-  b.l1 = a.f(p2 * c2);
-  b.u1 = a.f(p2 * c2);
-  size_t mx = p2 * (size_t)(c1 > c2 ? c1 : c2);
-  mx = p4 * c3 > mx ? p4 * c3 : mx;
-  *raw = a.f(mx);                                        // raw convolution output ahead of each BatchNorm
-  *bn_scratch = a.raw(opp_bn_train_scratch_bytes((int)p2, 256));
-  return a.off;
-}
-
-int backbone_train_impl(opp_ctx* c, const float* image, int B, int H, int W, float* feat_c, float* feat_f, float* bn_stats,
-                        Arena& a, hipStream_t s) {
-  OPP_CHECK_ARG(c && c->packed && c->train_packed, "backbone_train: training weights not packed (opp_pack_train_weights)");
-  OPP_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_train: bad B / H / W (%d, %dx%d)", B, H, W);
-  BackboneBufs b;
-  float* raw;
-  void* scratch;
-  plan_backbone_train(c, B, H, W, a, b, &raw, &scratch);
-  if (!a.ok) {
-    opp_set_error("backbone_train: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
-  const int hp = gemm_prec(c->cfg);
-  const float eps = 1e-5f;
-  // conv -> BatchNorm(batch statistics) -> (+ residual) -> activation   (resnet.py:37-45, :143, :153, :157)
-  auto conv_bn = [&](const float* x, int Hin, int Win, const ConvDesc& d, int stride, const float* res, int act, float* y) -> int {
-    const int Ho = (Hin + 2 * (d.ks / 2) - d.ks) / stride + 1, Wo = (Win + 2 * (d.ks / 2) - d.ks) / stride + 1;
-    OPP_TRY(run_conv(x, Hin, Win, d, stride, nullptr, OPP_RES_NONE, OPP_ACT_NONE, raw, s, hp, -1, B, true));
-    return opp_bn_train(raw, B * Ho * Wo, d.cout_pad(), d.cout, d.gamma, d.beta, eps, res, act, y,
-                        bn_stats ? bn_stats + (size_t)d.bn_slot * 512 : nullptr, scratch, s);
-  };
-  auto block = [&](const float* x, int Hin, int Win, const BlockDesc& bd, int stride, float* tmp, float* ds, float* y) -> int {
-    const int Ho = Hin / stride, Wo = Win / stride;
-    OPP_TRY(conv_bn(x, Hin, Win, bd.conv1, stride, nullptr, OPP_ACT_RELU, tmp));
-    const float* shortcut = x;
-    if (bd.has_down) {
-      OPP_TRY(conv_bn(x, Hin, Win, bd.down, stride, nullptr, OPP_ACT_NONE, ds));
-      shortcut = ds;
-    }
-    return conv_bn(tmp, Ho, Wo, bd.conv2, 1, shortcut, OPP_ACT_RELU, y);
-  };
-  OPP_TRY(opp_stem_im2col(image, B, H, W, b.col, s));
-  {
-    OppGemm g;
-    g.nonfinite = t_status_flag;
-  g.tile_policy = t_tile_policy;
-    g.A0 = b.col;
-    g.lda0 = 64;
-    g.ksplit = 64;
-    g.W = c->stem.w_train;
-    g.ldw = (int)split_floats(64, hp);
-    g.M = B * H2 * W2;
-    g.N = c->stem.cout;
-    g.K = 64;
-    g.C = raw;
-    g.ldc = pad32(c->stem.cout);
-    g.n_store = pad32(c->stem.cout);
-    g.prec = hp;
-    g.h2_inv = hp == OPP_PREC_FP16X2 ? c->stem.h2s_train + 1 : nullptr;
-    OPP_TRY(opp_gemm_launch(g, s));
-    OPP_TRY(opp_bn_train(raw, B * H2 * W2, pad32(c->stem.cout), c->stem.cout, c->stem.gamma, c->stem.beta, eps, nullptr, OPP_ACT_RELU,
-                         b.x0, bn_stats ? bn_stats + (size_t)c->stem.bn_slot * 512 : nullptr, scratch, s));
-  }
-  OPP_TRY(block(b.x0, H2, W2, c->blocks[0], 1, b.t1, nullptr, b.x1a));
-  OPP_TRY(block(b.x1a, H2, W2, c->blocks[1], 1, b.t1, nullptr, b.x1));
-  OPP_TRY(block(b.x1, H2, W2, c->blocks[2], 2, b.t2, b.ds2, b.x2a));
-  OPP_TRY(block(b.x2a, H4, W4, c->blocks[3], 1, b.t2, nullptr, b.x2));
-  OPP_TRY(block(b.x2, H4, W4, c->blocks[4], 2, b.t3, b.ds3, b.x3a));
-  OPP_TRY(block(b.x3a, H8, W8, c->blocks[5], 1, b.t3, nullptr, b.x3));
-  // FPN: the laterals and the last convolutions have no BatchNorm -> same kernels as in eval mode, batched
-  OPP_TRY(run_conv(b.x3, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, -1, B));
-  OPP_TRY(run_conv(b.x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l2, s, hp, -1, B));
-  OPP_TRY(conv_bn(b.l2, H4, W4, c->l2_out2a, 1, nullptr, OPP_ACT_LEAKY, b.u2));
-  OPP_TRY(run_conv(b.u2, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.x2o, s, hp, -1, B));
-  OPP_TRY(run_conv(b.x1, H2, W2, c->l1_out, 1, b.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l1, s, hp, -1, B));
-  OPP_TRY(conv_bn(b.l1, H2, W2, c->l1_out2a, 1, nullptr, OPP_ACT_LEAKY, b.u1));
-  OPP_TRY(run_conv(b.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp, -1, B));
-  return OPP_OK;
-}
-
-}  // namespace
-
-extern "C" size_t opp_backbone_train_workspace_bytes(const opp_ctx* ctx, int B, int H, int W) {
-  if (!ctx) return 0;
-  Arena a(nullptr, 0);
-  BackboneBufs b;
-  float* raw;
-  void* sc;
-  return opp_align(plan_backbone_train(ctx, B, H, W, a, b, &raw, &sc)) + 256;
-}
-
-extern "C" int opp_backbone_train(opp_ctx* ctx, const float* image, int B, int H, int W, float* feat_c, float* feat_f,
-                                  float* bn_stats, void* ws, size_t ws_bytes, void* stream) {
-  FlagScope flag_scope(ctx);
-  OPP_CHECK_ARG(ctx && image && feat_c && feat_f && ws, "backbone_train: null argument");
-  Arena a(ws, ws_bytes);
-  return backbone_train_impl(ctx, image, B, H, W, feat_c, feat_f, bn_stats, a, (hipStream_t)stream);
-}
-
 // ----------------------------------------------------------------------------------------
-// training step: backbone forward that KEEPS what its backward needs (the "tape"), and that backward
+// training mode: ResNetFPN_8_2.forward with BatchNorm batch statistics, B images per call (opp_backbone_train), the same forward
+// KEEPING what its backward needs (opp_backbone_train_tape: the "tape"), and that backward
 // (PL_OnePosePlus.training_step, lightning_model:54-81, differentiating ResNetFPN_8_2.forward, resnet.py:141-164)
 // ----------------------------------------------------------------------------------------
 namespace {
@@ -1051,80 +961,102 @@ size_t plan_tape(const opp_ctx* c, int B, int H, int W, Arena& a, Tape& t) {
   return a.off;
 }
 
-size_t plan_tape_ws(const opp_ctx* c, int B, int H, int W, Arena& a, float** col, float** dsbuf, void** scratch) {
+// What backbone_train_walk writes: a Tape, whose slots may alias each other where nothing reads them later, and what the walk needs beside it
+struct TrainBufs {
+  Tape t = {};        // t.stats may be null: batch mean / rstd are not kept
+  float* ds[6] = {};  // shortcut of block i = BatchNorm output of its downsample branch (blocks with one); may be one shared buffer
+  float* col = nullptr;         // im2col rows of the stem
+  void* bn_scratch = nullptr;
+};
+
+// workspace of opp_backbone_train_tape: everything the backward reads lives in the tape, the rest here
+size_t plan_tape_ws(const opp_ctx* c, int B, int H, int W, Arena& a, TrainBufs& v) {
   const size_t p2 = (size_t)B * (H / 2) * (W / 2), p4 = (size_t)B * (H / 4) * (W / 4);
-  *col = a.f(p2 * 64);
-  *dsbuf = a.f(p4 * pad32(c->cfg.block_dims[2] > c->cfg.block_dims[1] ? c->cfg.block_dims[2] : c->cfg.block_dims[1]));
-  *scratch = a.raw(opp_bn_train_scratch_bytes((int)p2, 256));
+  v.col = a.f(p2 * 64);
+  float* dsbuf = a.f(p4 * pad32(c->cfg.block_dims[2] > c->cfg.block_dims[1] ? c->cfg.block_dims[2] : c->cfg.block_dims[1]));
+  for (float*& d : v.ds) d = dsbuf;
+  v.bn_scratch = a.raw(opp_bn_train_scratch_bytes((int)p2, 256));
   return a.off;
 }
 
-int backbone_tape_impl(opp_ctx* c, const float* image, int B, int H, int W, float* feat_c, float* feat_f, float* bn_stats, Tape& t,
-                       Arena& a, hipStream_t s) {
-  OPP_CHECK_ARG(c && c->packed && c->train_packed, "backbone_train_tape: training weights not packed (opp_pack_train_weights)");
-  OPP_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_train_tape: bad B / H / W (%d, %dx%d)", B, H, W);
-  float *col, *dsbuf;
-  void* scratch;
-  plan_tape_ws(c, B, H, W, a, &col, &dsbuf, &scratch);
-  if (!a.ok) {
-    opp_set_error("backbone_train_tape: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+// workspace of opp_backbone_train, which keeps nothing: the maps of the eval-mode walk (two ping-pong maps per resolution) and ONE buffer
+// for the raw convolution output ahead of each BatchNorm -- every raw slot of the view is that buffer (one stream: written, normalised, reused)
+size_t plan_backbone_train(const opp_ctx* c, int B, int H, int W, Arena& a, TrainBufs& v) {
+  BackboneBufs b;
+  plan_backbone(c, B, H, W, false, a, b);
+  const size_t p2 = (size_t)B * (H / 2) * (W / 2), p4 = (size_t)B * (H / 4) * (W / 4);
+  const int c1 = pad32(c->cfg.block_dims[0]), c2 = pad32(c->cfg.block_dims[1]), c3 = pad32(c->cfg.block_dims[2]);
+  size_t mx = p2 * (size_t)(c1 > c2 ? c1 : c2);
+  mx = p4 * c3 > mx ? p4 * c3 : mx;
+  float* raw = a.f(mx);
+  v.bn_scratch = a.raw(opp_bn_train_scratch_bytes((int)p2, 256));
+  v.col = b.col;
+  v.ds[2] = b.ds2;
+  v.ds[4] = b.ds3;
+  // two ping-pong maps per resolution, as in the eval-mode walk; the blocks with a downsample branch are 2 and 4
+  float* const tmp[6] = {b.t1, b.t1, b.t2, b.t2, b.t3, b.t3};
+  float* const out[6] = {b.x1a, b.x1, b.x2a, b.x2, b.x3a, b.x3};
+  Tape& t = v.t;
+  for (int i = 0; i < 6; ++i) t.blk[i] = {.raw1 = raw, .t = tmp[i], .raw2 = raw, .rawd = c->blocks[i].has_down ? raw : nullptr, .y = out[i]};
+  t.raw0 = t.raw_u2 = t.raw_u1 = raw;
+  t.x0 = b.x0;
+  t.l2 = b.l2;
+  t.u2 = b.u2;
+  t.x2o = b.x2o;
+  t.l1 = b.l1;
+  t.u1 = b.u1;
+  t.stats = nullptr;
+  return a.off;
+}
+
+// ResNetFPN_8_2.forward in train() mode (BatchNorm batch statistics), B images per call: both training entries.  Every raw convolution
+// output and activation goes where the view says; bn_stats (optional) receives what the running statistics are updated from.
+int backbone_train_walk(opp_ctx* c, const float* image, int B, int H, int W, float* feat_c, float* feat_f, float* bn_stats, const TrainBufs& v,
+                        hipStream_t s) {
+  const Tape& t = v.t;
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
   const int hp = gemm_prec(c->cfg);
   const float eps = 1e-5f;
-  auto conv_bn = [&](const float* x, int Hin, int Win, const ConvDesc& d, int stride, const float* res, int act, float* raw, float* y) -> int {
-    const int Ho = (Hin + 2 * (d.ks / 2) - d.ks) / stride + 1, Wo = (Win + 2 * (d.ks / 2) - d.ks) / stride + 1;
-    OPP_TRY(run_conv(x, Hin, Win, d, stride, nullptr, OPP_RES_NONE, OPP_ACT_NONE, raw, s, hp, -1, B, true));
-    float* st = t.stats + (size_t)d.bn_slot * 512;
-    return opp_bn_train(raw, B * Ho * Wo, d.cout_pad(), d.cout, d.gamma, d.beta, eps, res, act, y,
-                        bn_stats ? bn_stats + (size_t)d.bn_slot * 512 : nullptr, scratch, s, st, st + 256);
+  const ConvOpts batched = {.Bn = B}, batched_raw = {.Bn = B, .raw = true};
+  // BatchNorm(batch statistics) of convolution d's raw output -> (+ residual) -> activation
+  auto bn = [&](const ConvDesc& d, const float* raw, int rows, const float* res, int act, float* y) -> int {
+    float* st = t.stats ? t.stats + (size_t)d.bn_slot * 512 : nullptr;
+    return opp_bn_train(raw, rows, d.cout_pad(), d.cout, d.gamma, d.beta, eps, res, act, y, bn_stats ? bn_stats + (size_t)d.bn_slot * 512 : nullptr,
+                        v.bn_scratch, s, st, st ? st + 256 : nullptr);
   };
-  auto block = [&](const float* x, int Hin, int Win, const BlockDesc& bd, int stride, TapeBlock& tb) -> int {
+  // conv -> BatchNorm -> (+ residual) -> activation   (resnet.py:37-45, :143, :153, :157)
+  auto conv_bn = [&](const float* x, int Hin, int Win, const ConvDesc& d, int stride, const float* res, int act, float* raw, float* y) -> int {
+    OPP_TRY(run_conv(x, Hin, Win, d, stride, nullptr, OPP_RES_NONE, OPP_ACT_NONE, raw, s, hp, batched_raw));
+    return bn(d, raw, B * conv_out(Hin, d.ks, stride) * conv_out(Win, d.ks, stride), res, act, y);
+  };
+  auto block = [&](const float* x, int Hin, int Win, const BlockDesc& bd, int stride, const TapeBlock& tb, float* ds) -> int {
     const int Ho = Hin / stride, Wo = Win / stride;
     OPP_TRY(conv_bn(x, Hin, Win, bd.conv1, stride, nullptr, OPP_ACT_RELU, tb.raw1, tb.t));
     const float* shortcut = x;
     if (bd.has_down) {
-      OPP_TRY(conv_bn(x, Hin, Win, bd.down, stride, nullptr, OPP_ACT_NONE, tb.rawd, dsbuf));
-      shortcut = dsbuf;
+      OPP_TRY(conv_bn(x, Hin, Win, bd.down, stride, nullptr, OPP_ACT_NONE, tb.rawd, ds));
+      shortcut = ds;
     }
     return conv_bn(tb.t, Ho, Wo, bd.conv2, 1, shortcut, OPP_ACT_RELU, tb.raw2, tb.y);
   };
-  OPP_TRY(opp_stem_im2col(image, B, H, W, col, s));
-  {
-    OppGemm g;
-    g.tile_policy = t_tile_policy;
-    g.A0 = col;
-    g.lda0 = 64;
-    g.ksplit = 64;
-    g.W = c->stem.w_train;
-    g.ldw = (int)split_floats(64, hp);
-    g.M = B * H2 * W2;
-    g.N = c->stem.cout;
-    g.K = 64;
-    g.C = t.raw0;
-    g.ldc = pad32(c->stem.cout);
-    g.n_store = pad32(c->stem.cout);
-    g.prec = hp;
-    OPP_TRY(opp_gemm_launch(g, s));
-    float* st = t.stats + (size_t)c->stem.bn_slot * 512;
-    OPP_TRY(opp_bn_train(t.raw0, B * H2 * W2, pad32(c->stem.cout), c->stem.cout, c->stem.gamma, c->stem.beta, eps, nullptr, OPP_ACT_RELU,
-                         t.x0, bn_stats ? bn_stats + (size_t)c->stem.bn_slot * 512 : nullptr, scratch, s, st, st + 256));
-  }
-  OPP_TRY(block(t.x0, H2, W2, c->blocks[0], 1, t.blk[0]));
-  OPP_TRY(block(t.blk[0].y, H2, W2, c->blocks[1], 1, t.blk[1]));
-  OPP_TRY(block(t.blk[1].y, H2, W2, c->blocks[2], 2, t.blk[2]));
-  OPP_TRY(block(t.blk[2].y, H4, W4, c->blocks[3], 1, t.blk[3]));
-  OPP_TRY(block(t.blk[3].y, H4, W4, c->blocks[4], 2, t.blk[4]));
-  OPP_TRY(block(t.blk[4].y, H8, W8, c->blocks[5], 1, t.blk[5]));
+  OPP_TRY(opp_stem_im2col(image, B, H, W, v.col, s));
+  OPP_TRY(opp_gemm_launch(stem_gemm(c, v.col, B * H2 * W2, c->stem.w_train, c->stem.h2s_train, nullptr, OPP_ACT_NONE, t.raw0), s));
+  OPP_TRY(bn(c->stem, t.raw0, B * H2 * W2, nullptr, OPP_ACT_RELU, t.x0));
+  OPP_TRY(block(t.x0, H2, W2, c->blocks[0], 1, t.blk[0], v.ds[0]));
+  OPP_TRY(block(t.blk[0].y, H2, W2, c->blocks[1], 1, t.blk[1], v.ds[1]));
+  OPP_TRY(block(t.blk[1].y, H2, W2, c->blocks[2], 2, t.blk[2], v.ds[2]));
+  OPP_TRY(block(t.blk[2].y, H4, W4, c->blocks[3], 1, t.blk[3], v.ds[3]));
+  OPP_TRY(block(t.blk[3].y, H4, W4, c->blocks[4], 2, t.blk[4], v.ds[4]));
+  OPP_TRY(block(t.blk[4].y, H8, W8, c->blocks[5], 1, t.blk[5], v.ds[5]));
   const float *x1 = t.blk[1].y, *x2 = t.blk[3].y, *x3 = t.blk[5].y;
-  OPP_TRY(run_conv(x3, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, -1, B));
-  OPP_TRY(run_conv(x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, t.l2, s, hp, -1, B));
+  // FPN: the laterals and the last convolutions have no BatchNorm -> same kernels as in eval mode, batched
+  OPP_TRY(run_conv(x3, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, batched));
+  OPP_TRY(run_conv(x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, t.l2, s, hp, batched));
   OPP_TRY(conv_bn(t.l2, H4, W4, c->l2_out2a, 1, nullptr, OPP_ACT_LEAKY, t.raw_u2, t.u2));
-  OPP_TRY(run_conv(t.u2, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, t.x2o, s, hp, -1, B));
-  OPP_TRY(run_conv(x1, H2, W2, c->l1_out, 1, t.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, t.l1, s, hp, -1, B));
+  OPP_TRY(run_conv(t.u2, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, t.x2o, s, hp, batched));
+  OPP_TRY(run_conv(x1, H2, W2, c->l1_out, 1, t.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, t.l1, s, hp, batched));
   OPP_TRY(conv_bn(t.l1, H2, W2, c->l1_out2a, 1, nullptr, OPP_ACT_LEAKY, t.raw_u1, t.u1));
-  OPP_TRY(run_conv(t.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp, -1, B));
+  OPP_TRY(run_conv(t.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp, batched));
   return OPP_OK;
 }
 
@@ -1140,7 +1072,7 @@ struct ConvBwdWs {
 struct ConvBwdNeed { size_t wt_tmp = 0, wt_pack = 0, wt_split = 0, wt_tail = 0, zbuf = 0, geo = 0, wg = 0; };
 
 void conv_bwd_need(ConvBwdNeed& n, int B, int Hin, int Win, int cin, int cout, int ks, int stride, bool need_dx, bool need_dw, int prec) {
-  const int Ho = (Hin + 2 * (ks / 2) - ks) / stride + 1, Wo = (Win + 2 * (ks / 2) - ks) / stride + 1;
+  const int Ho = conv_out(Hin, ks, stride), Wo = conv_out(Win, ks, stride);
   auto mx = [](size_t& a, size_t b) { a = b > a ? b : a; };
   if (need_dx) {
     mx(n.wt_tmp, (size_t)cout * cin * ks * ks);
@@ -1173,7 +1105,7 @@ int conv_backward(const float* x, int B, int Hin, int Win, int cin, const float*
   OPP_CHECK_ARG(stride == 1 || (stride == 2 && Hin % 2 == 0 && Win % 2 == 0), "conv_backward: stride must be 1 or 2 (even input size)");
   OPP_CHECK_ARG(prec == OPP_PREC_FP32 || prec == OPP_PREC_BF16X3, "conv_backward: arithmetic must be fp32 or bf16x3");
   const int pad = ks / 2;
-  const int Ho = (Hin + 2 * pad - ks) / stride + 1, Wo = (Win + 2 * pad - ks) / stride + 1;
+  const int Ho = conv_out(Hin, ks, stride), Wo = conv_out(Win, ks, stride);
   const int cin_pad = pad32(cin), cout_pad = pad32(cout);
   if (dw) {
     const void* geo = nullptr;
@@ -1365,9 +1297,8 @@ extern "C" size_t opp_backbone_tape_bytes(const opp_ctx* ctx, int B, int H, int 
 extern "C" size_t opp_backbone_train_tape_workspace_bytes(const opp_ctx* ctx, int B, int H, int W) {
   if (!ctx) return 0;
   Arena a(nullptr, 0);
-  float *col, *ds;
-  void* sc;
-  return opp_align(plan_tape_ws(ctx, B, H, W, a, &col, &ds, &sc)) + 256;
+  TrainBufs v;
+  return opp_align(plan_tape_ws(ctx, B, H, W, a, v)) + 256;
 }
 
 extern "C" int opp_backbone_train_tape(opp_ctx* ctx, const float* image, int B, int H, int W, float* feat_c, float* feat_f, float* bn_stats,
@@ -1376,11 +1307,41 @@ extern "C" int opp_backbone_train_tape(opp_ctx* ctx, const float* image, int B, 
   OPP_CHECK_ARG(ctx && image && feat_c && feat_f && tape && ws, "backbone_train_tape: null argument");
   OPP_CHECK_ARG(gemm_prec(ctx->cfg) != OPP_PREC_FP16X2, "backbone_train_tape: the training step runs in bf16x3 or fp32");
   Arena ta(tape, tape_bytes);
-  Tape t;
-  plan_tape(ctx, B, H, W, ta, t);
+  TrainBufs v;
+  plan_tape(ctx, B, H, W, ta, v.t);
   OPP_CHECK_ARG(ta.ok, "backbone_train_tape: tape buffer too small (%zu bytes)", tape_bytes);
+  OPP_CHECK_ARG(ctx->packed && ctx->train_packed, "backbone_train_tape: training weights not packed (opp_pack_train_weights)");
+  OPP_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_train_tape: bad B / H / W (%d, %dx%d)", B, H, W);
   Arena a(ws, ws_bytes);
-  return backbone_tape_impl(ctx, image, B, H, W, feat_c, feat_f, bn_stats, t, a, (hipStream_t)stream);
+  plan_tape_ws(ctx, B, H, W, a, v);
+  if (!a.ok) {
+    opp_set_error("backbone_train_tape: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
+  return backbone_train_walk(ctx, image, B, H, W, feat_c, feat_f, bn_stats, v, (hipStream_t)stream);
+}
+
+extern "C" size_t opp_backbone_train_workspace_bytes(const opp_ctx* ctx, int B, int H, int W) {
+  if (!ctx) return 0;
+  Arena a(nullptr, 0);
+  TrainBufs v;
+  return opp_align(plan_backbone_train(ctx, B, H, W, a, v)) + 256;
+}
+
+extern "C" int opp_backbone_train(opp_ctx* ctx, const float* image, int B, int H, int W, float* feat_c, float* feat_f,
+                                  float* bn_stats, void* ws, size_t ws_bytes, void* stream) {
+  FlagScope flag_scope(ctx);
+  OPP_CHECK_ARG(ctx && image && feat_c && feat_f && ws, "backbone_train: null argument");
+  OPP_CHECK_ARG(ctx->packed && ctx->train_packed, "backbone_train: training weights not packed (opp_pack_train_weights)");
+  OPP_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_train: bad B / H / W (%d, %dx%d)", B, H, W);
+  Arena a(ws, ws_bytes);
+  TrainBufs v;
+  plan_backbone_train(ctx, B, H, W, a, v);
+  if (!a.ok) {
+    opp_set_error("backbone_train: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
+  return backbone_train_walk(ctx, image, B, H, W, feat_c, feat_f, bn_stats, v, (hipStream_t)stream);
 }
 
 extern "C" size_t opp_backbone_backward_workspace_bytes(const opp_ctx* ctx, int B, int H, int W) {
@@ -1416,7 +1377,7 @@ extern "C" size_t opp_backbone_workspace_bytes(const opp_ctx* ctx, int H, int W)
   if (!ctx) return 0;
   Arena a(nullptr, 0);
   BackboneBufs b;
-  return opp_align(plan_backbone(ctx, H, W, a, b)) + 256;
+  return opp_align(plan_backbone(ctx, 1, H, W, true, a, b)) + 256;
 }
 
 extern "C" int opp_backbone(opp_ctx* ctx, const float* image, int H, int W, float* feat_c, float* feat_f, void* ws,
@@ -2263,12 +2224,13 @@ extern "C" int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_o
   const int split_a = conv_splits_by_shape(ctx->l1_out2a, dense_px, hp) ? 1 : 0, split_b = conv_splits_by_shape(ctx->l1_out2b, dense_px, hp) ? 1 : 0;
   // l1 patch = conv1x1(x1 patch) + up2x(x2_out) at the patch pixels (out-of-image pixels: exact zeros)
   OPP_TRY(opp_fine_patch_gather(x1, Hf, Wf, c1, x2_out, c2, j_ids, M, wc, stride, org - 2, P9, b.xa, b.l1, s));
-  OPP_TRY(run_conv(b.xa, P9, P9, ctx->l1_out, 1, b.l1, OPP_RES_DIRECT, OPP_ACT_NONE, b.l1, s, hp, -1, M, false, 0, 0));   // (K = 4 chunks: never split)
+  OPP_TRY(run_conv(b.xa, P9, P9, ctx->l1_out, 1, b.l1, OPP_RES_DIRECT, OPP_ACT_NONE, b.l1, s, hp,
+                   {.Bn = M, .pad = 0, .splitk_force = 0}));   // (K = 4 chunks: never split)
   // u1 patch = LeakyReLU(BN(conv3x3(l1))) on (W+2)^2 pixels; pixels outside the image are the NEXT convolution's zero padding
-  OPP_TRY(run_conv(b.l1, P9, P9, ctx->l1_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, b.u1, s, hp, -1, M, false, 0, split_a));
+  OPP_TRY(run_conv(b.l1, P9, P9, ctx->l1_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, b.u1, s, hp, {.Bn = M, .pad = 0, .splitk_force = split_a}));
   OPP_TRY(opp_patch_zero_oob(b.u1, c2, j_ids, M, wc, stride, org - 1, P7, Hf, Wf, s));
   // the W x W window of the fine map, written as the match's window tokens; window cells outside the image are the unfold's zero padding
-  OPP_TRY(run_conv(b.u1, P7, P7, ctx->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.X, s, hp, -1, M, false, 0, split_b));
+  OPP_TRY(run_conv(b.u1, P7, P7, ctx->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.X, s, hp, {.Bn = M, .pad = 0, .splitk_force = split_b}));
   OPP_TRY(opp_patch_zero_oob(b.X, C, j_ids, M, wc, stride, org, Wwin, Hf, Wf, s));
   OPP_TRY(opp_fine_points_gather(bank_f, n, i_ids, M, C, b.X + (size_t)M * WW * C, C, s));
   return fine_tail(ctx, b.X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, a, s);
@@ -2346,7 +2308,7 @@ extern "C" int opp_conv2d_nhwc(const float* x, int Hin, int Win, int cin, const 
   d.w = const_cast<float*>(w_packed);
   d.bias = const_cast<float*>(bias);
   d.h2s = const_cast<float*>(h2_scale);
-  return run_conv(x, Hin, Win, d, stride, residual, res_mode, act, y, (hipStream_t)stream, prec, tile_cfg);
+  return run_conv(x, Hin, Win, d, stride, residual, res_mode, act, y, (hipStream_t)stream, prec, {.tile_cfg = tile_cfg});
 }
 
 extern "C" int opp_conv2d_nhwc_split(const float* x, const void* x_split, int Hin, int Win, int cin, const float* w_packed, const float* bias,
@@ -2362,7 +2324,8 @@ extern "C" int opp_conv2d_nhwc_split(const float* x, const void* x_split, int Hi
   d.w = const_cast<float*>(w_packed);
   d.bias = const_cast<float*>(bias);
   OPP_CHECK_ARG(x || conv_takes_split(d, OPP_PREC_BF16X3), "conv2d_split: a 3x3 convolution over 32 n + (1..4) channels packs its K tail and needs the fp32 input");
-  return run_conv(x, Hin, Win, d, stride, residual, res_mode, act, y, (hipStream_t)stream, OPP_PREC_BF16X3, tile_cfg, 1, false, -1, -1, x_split, y_split);
+  return run_conv(x, Hin, Win, d, stride, residual, res_mode, act, y, (hipStream_t)stream, OPP_PREC_BF16X3,
+                  {.tile_cfg = tile_cfg, .x3 = x_split, .y3 = y_split});
 }
 
 extern "C" int opp_pack_conv_weight(const float* w, const float* scale, int cout, int cin, int ks, int cout_pad, int cin_pad,

@@ -246,3 +246,24 @@ def test_tile_policy_guards():
     assert lib.opp_gemm_tile_for(65536, 196, 224, _k3(196), 1, 1, 0) != 27       # nor fp16x2
     for bad in [(0, 1, 128, 128, 1, 2, 0), (128, 1, 128, 100, 1, 2, 0), (128, 1, 128, 128, 1, 5, 0), (128, 1, 128, 128, 1, 2, 7)]:
         assert lib.opp_gemm_tile_for(*bad) < 0
+
+
+# (B, H, W) -> opp_backbone_tape_bytes, opp_backbone_train_tape_workspace_bytes of the default configuration, recorded from the build of
+# commit 9537b0a.  tests/test_train_bwd_gpu.py builds views on this layout.
+TAPE_BYTES = {(1, 128, 128): (46696704, 2164992), (4, 512, 512): (2986379520, 138414336)}
+
+
+@pytest.mark.parametrize("shape", sorted(TAPE_BYTES), ids=lambda s: "B%d_%dx%d" % s)
+def test_tape_layout_sizes_are_pinned(shape):
+    """The tape of the training step is a contract between opp_backbone_train_tape, opp_backbone_backward and the callers that
+    slice it: its size and that of the forward's workspace are host arithmetic (no device needed) and must not move."""
+    import ctypes
+    from onepose_plus_plus_amd import _lib
+    lib = _lib.load()
+    ctx = ctypes.c_void_p()
+    ccfg = OnePosePlus_model(default_config())._c_config()
+    _lib.check(lib.opp_create(ctypes.byref(ccfg), ctypes.byref(ctx)), "opp_create")
+    try:
+        assert (lib.opp_backbone_tape_bytes(ctx, *shape), lib.opp_backbone_train_tape_workspace_bytes(ctx, *shape)) == TAPE_BYTES[shape]
+    finally:
+        lib.opp_destroy(ctx)
