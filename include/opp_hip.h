@@ -209,6 +209,10 @@ int opp_set_object_prefix(opp_ctx* ctx, const void* prefix, int n_points);
 size_t opp_transformer_workspace_bytes(const opp_ctx* ctx, int which, int n_seg, int len0, int len1);
 int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg, int len0, int len1,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* Test aid: byte offsets, inside the workspace of opp_transformer for the same arguments, of the linear attention's reduced
+ * KV [2][n_seg][d_model * d_head] and Ksum [2][n_seg][d_model] (stream 0 first).  After opp_transformer they hold the sums the LAST
+ * layer applied (linear attention only). */
+int opp_transformer_kv_offsets(const opp_ctx* ctx, int which, int n_seg, int len0, int len1, size_t* kv_offset, size_t* ks_offset);
 
 /* CoarseMatching.forward + get_coarse_match, inference branch (utils/coarse_matching.py:76-242).
  * feat2d [L][C], feat3d [N][C]; conf [N][L] is written (data['conf_matrix']).  Outputs have

@@ -77,6 +77,7 @@ SIGNATURES = {
                                   c_void_p, c_size_t, c_void_p]),
     "opp_transformer_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "opp_transformer": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "opp_transformer_kv_offsets": (c_int, [c_void_p, c_int, c_int, c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "opp_coarse_match_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "opp_coarse_match": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_float, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1670,6 +1670,9 @@ int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cros
   const float eps_attn = 1e-6f, eps_ln = 1e-5f;
   static const int fuse_env = getenv("OPP_FUSE_LN") ? atoi(getenv("OPP_FUSE_LN")) : 1;   // tuning knob
   const bool fuse_ln = fuse_env && (C == 256 || C == 128);
+  // OPP_KV_FOLD=0: every layer launches the stand-alone KV gather (A/B switch of the tools and of tests/test_kv_fold_gpu.py, read per call)
+  const bool kv_fold_env = !(getenv("OPP_KV_FOLD") && getenv("OPP_KV_FOLD")[0] == '0');
+  bool kv_parts = false;      // the previous layer's kernel left this layer's KV / Ksum chunk partials in b.scratch
   for (size_t li = 0; li < layers.size(); ++li) {
     const EncLayerDesc& e = layers[li];
     const bool cross = is_cross[li] != 0;
@@ -1714,7 +1717,9 @@ int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cros
     // everything behind the projection in ONE launch (bf16x3): [apply ->] merge -> norm1 -> mlp.0 -> ReLU -> mlp.2 -> norm2 -> +x
     const bool chain_apply = n_seg == 1 && C == 256 && D == 32;     // coarse level: the kernel applies KV itself
     if (fusion && h2 == OPP_PREC_BF16X3 && e.fmerge && opp_enc_chain_ok(C, nhead, chain_apply)) {
-      OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, l1_qkv, cross, b.kv, b.ks, b.scratch, chain_apply ? nullptr : b.msg, eps_attn, s));
+      if (kv_parts) OPP_TRY(opp_linattn_reduce_chunks(len0, l1_qkv, b.kv, b.ks, b.scratch, s));     // the gather ran inside layer li - 1
+      else OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, l1_qkv, cross, b.kv, b.ks, b.scratch, chain_apply ? nullptr : b.msg, eps_attn, s));
+      kv_parts = false;
       OppEncChain ch;
       ch.C = C;
       ch.X = X;
@@ -1733,6 +1738,13 @@ int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cros
         ch.qkv_out = b.qkv;
         ch.qkv_out1 = (prefix_mode == OPP_PREFIX_MAKE && li == 0) ? pre->qkv1 : nullptr;
         ch.qmask = mask0;
+        // ... and reduces its tile's phi(K)^T V, sum phi(K) for layer li + 1 (the rows layer li + 1 reduces are the rows this launch
+        // projects).  The object-prefix builder keeps the gather: its projection rows are part of the prefix blob
+        const int l1_next = (prefix_mode == OPP_PREFIX_USE && li + 1 < 2) ? 0 : len1;
+        if (kv_fold_env && chain_apply && fusion == 2 && prefix_mode != OPP_PREFIX_MAKE && layers[li + 1].fmerge && ch.len1 == l1_next) {
+          opp_linattn_chunk_parts(b.scratch, ch.len0, ch.len1, &ch.kv_part, &ch.ks_part);
+          kv_parts = true;
+        }
       }
       ch.msg = b.msg;
       ch.ldm = C;
@@ -1868,6 +1880,19 @@ extern "C" size_t opp_transformer_workspace_bytes(const opp_ctx* ctx, int which,
   Arena a(nullptr, 0);
   TrBufs b;
   return opp_align(plan_transformer(C, C / nh, n_seg, len0, len1, a, b)) + 256;
+}
+
+extern "C" int opp_transformer_kv_offsets(const opp_ctx* ctx, int which, int n_seg, int len0, int len1, size_t* kv_offset, size_t* ks_offset) {
+  OPP_CHECK_ARG(ctx && kv_offset && ks_offset && (which == 0 || which == 1), "transformer_kv_offsets: bad argument");
+  const int C = which == 0 ? ctx->cfg.coarse_d_model : ctx->cfg.fine_d_model;
+  const int nh = which == 0 ? ctx->cfg.coarse_nhead : ctx->cfg.fine_nhead;
+  char* const base = reinterpret_cast<char*>(uintptr_t(1) << 20);     // never dereferenced: the plan only adds offsets to it
+  Arena a(base, ~size_t(0) >> 1);
+  TrBufs b;
+  plan_transformer(C, C / nh, n_seg, len0, len1, a, b);
+  *kv_offset = (size_t)(reinterpret_cast<char*>(b.kv) - base);
+  *ks_offset = (size_t)(reinterpret_cast<char*>(b.ks) - base);
+  return OPP_OK;
 }
 
 extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg, int len0, int len1, void* ws,

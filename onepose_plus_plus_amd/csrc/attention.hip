@@ -404,22 +404,36 @@ __global__ __launch_bounds__(256) void linattn_kv_mfma_kernel(const float* __res
 
 // out_kv [2][8192], out_ks [2][256] ; blockIdx.y = stream.  Block = 64 outputs x 4 chunk groups (group g sums
 // chunks g, g+4, ... in order; the four group sums are added in group order): fixed order, 4x shorter chains.
+// PER_CHUNK = false: one partial per workgroup of linattn_kv_mfma_kernel (kPairGroup chunks already summed), n0 / n1 = partials per stream.
+// PER_CHUNK = true: one partial per 64-token chunk, written by enc_layer64_kernel (enc_layer64.hip, step 8), n0 / n1 = chunks per stream;
+// the kPairGroup chunks of a group are summed first, (c0 + c1) + (c2 + c3) with the chunks behind the stream's end as zeros -- the sum
+// linattn_kv_mfma_kernel forms through LDS -- so both modes add the same numbers in the same order.
+template <bool PER_CHUNK>
 __global__ __launch_bounds__(256) void linattn_reduce_pair_kernel(const float* __restrict__ kv_part,
-                                                                 const float* __restrict__ ks_part, int chunks0,
-                                                                 int chunks1, float* __restrict__ out_kv,
+                                                                 const float* __restrict__ ks_part, int n0,
+                                                                 int n1, float* __restrict__ out_kv,
                                                                  float* __restrict__ out_ks) {
   constexpr int KV = 8192, C = 256;
   __shared__ float red[4][64];
   const int stream = blockIdx.y;
-  const int c_begin = stream ? chunks0 : 0;
-  const int c_end = stream ? chunks0 + chunks1 : chunks0;
+  const int c_begin = stream ? n0 : 0;
+  const int c_end = stream ? n0 + n1 : n0;
   const int e = threadIdx.x & 63, gq = threadIdx.x >> 6;
   const int i = blockIdx.x * 64 + e;
+  const float* part = i < KV ? kv_part + i : ks_part + (i - KV);
+  const size_t width = i < KV ? KV : C;
   float s = 0.f;
-  if (i < KV) {
-    for (int c = c_begin + gq; c < c_end; c += 4) s += kv_part[(size_t)c * KV + i];
-  } else if (i < KV + C) {
-    for (int c = c_begin + gq; c < c_end; c += 4) s += ks_part[(size_t)c * C + (i - KV)];
+  if (i < KV + C) {
+    if constexpr (PER_CHUNK) {
+      for (int c = c_begin + gq * kPairGroup; c < c_end; c += 4 * kPairGroup) {
+        float p[kPairGroup];
+#pragma unroll
+        for (int w = 0; w < kPairGroup; ++w) p[w] = c + w < c_end ? part[(size_t)(c + w) * width] : 0.f;
+        s += (p[0] + p[1]) + (p[2] + p[3]);
+      }
+    } else {
+      for (int c = c_begin + gq; c < c_end; c += 4) s += part[(size_t)c * width];
+    }
   }
   red[gq][e] = s;
   __syncthreads();
@@ -608,9 +622,28 @@ int opp_linattn_kv_pair(const float* qkv, int ld, int len0, int len1, float* kv,
   }
   {  // algorithmic bytes: every chunk partial read once, KV / Ksum of both streams written
     OppProfScope prof(OPP_PROF_LINATTN_REDUCE, stream, (double)(c0 + c1 + 2) * (8192 + 256) * 4.0);
-    hipLaunchKernelGGL(linattn_reduce_pair_kernel, dim3(opp_cdiv(8192 + 256, 64), 2), dim3(256), 0, stream, kvp, ksp, c0, c1, kv, ks);
+    hipLaunchKernelGGL(linattn_reduce_pair_kernel<false>, dim3(opp_cdiv(8192 + 256, 64), 2), dim3(256), 0, stream, kvp, ksp, c0, c1, kv, ks);
   }
   OPP_CHECK_LAUNCH("linattn_kv_pair");
+  return OPP_OK;
+}
+
+// The chunk partials of the fused layer kernel (OppEncChain::kv_part / ks_part) live in the same scratch: kv partials of all chunks first
+void opp_linattn_chunk_parts(float* scratch, int len0, int len1, float** kv_part, float** ks_part) {
+  const size_t chunks = (size_t)opp_cdiv(len0, kPairChunk) + opp_cdiv(len1, kPairChunk);
+  *kv_part = scratch;
+  *ks_part = scratch + chunks * 8192;
+}
+
+// kv / ks of both streams from the per-chunk partials enc_layer64_kernel left in `scratch`: the bits of opp_linattn_kv_pair on the same rows
+int opp_linattn_reduce_chunks(int len0, int len1, float* kv, float* ks, float* scratch, hipStream_t stream) {
+  const int c0 = opp_cdiv(len0, kPairChunk), c1 = opp_cdiv(len1, kPairChunk);
+  if (c0 + c1 == 0) return OPP_OK;
+  float *kvp, *ksp;
+  opp_linattn_chunk_parts(scratch, len0, len1, &kvp, &ksp);
+  OppProfScope prof(OPP_PROF_LINATTN_REDUCE, stream, (double)(c0 + c1 + 2) * (8192 + 256) * 4.0);
+  hipLaunchKernelGGL(linattn_reduce_pair_kernel<true>, dim3(opp_cdiv(8192 + 256, 64), 2), dim3(256), 0, stream, kvp, ksp, c0, c1, kv, ks);
+  OPP_CHECK_LAUNCH("linattn_reduce_pair_kernel");
   return OPP_OK;
 }
 

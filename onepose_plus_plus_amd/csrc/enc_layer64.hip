@@ -13,6 +13,8 @@
 //   4. mlp.0 accumulators += merged . W1[:, 256:512]^T, ReLU
 //   5. hidden activation, 256 columns at a time -> operand tile -> mlp.2 accumulators (two K halves)
 //   6. norm2, + x (re-read in fp32), rows written.
+//   7. (optional) the next layer's q | k | v projection of the finished rows, wave = head;  8. (optional) the KV / Ksum partial of the
+//      tile for the next layer's linear attention, straight from the phi(K) and V / S accumulators.
 // The 64 x 512 hidden activation never exists outside the accumulators of the waves that own its columns.
 // LDS: operand tile 97 KB + fp32 staging [32][260] 32.5 KB + 1 KB = 130.5 KB, one 8-wave workgroup per CU.
 #include <stdlib.h>
@@ -49,11 +51,11 @@ __global__ __launch_bounds__(NT) void enc_layer64_kernel(const OppEncChain a) {
   // phi(Q) rows of this tile: stream 1 may come from its own buffer (the per-object prefix keeps the image-independent projection)
   const float* qrows = (stream && a.q1 != nullptr) ? a.q1 + (size_t)(cidx * R64) * a.ldq : a.q + (size_t)row0 * a.ldq;
 
-  // ---- GEMM over the operand tile: acc[i][j] += A[rows 32 i ..][k16-steps of the tile] * W[tile t0 + j][steps S0 .. S1)^T ----
+  // ---- GEMM over the operand tile: acc[i][j] += A[rows 32 i ..][k16-steps of the tile] * W[tile t0 + j * tstep][steps S0 .. S1)^T ----
   // weights fragment-major (opp_pack_frag_b3): ((t * KS + s) * 3 + part) * 1024 + lane * 16 bytes, KS = steps of the matrix;
   // operand-tile step = s - S0.  Six bf16 products per block, K ascending: the sequence of opp_gemm_kernel<bf16x3>.
   const char* a_lane = A + l31 * SA + half * 48;
-  auto gemm = [&](auto ntile_c, auto depth_c, auto s0_c, auto s1_c, auto ks_c, const void* wf, int t0, f32x16 (&acc)[2][decltype(ntile_c)::value]) {
+  auto gemm = [&](auto ntile_c, auto depth_c, auto s0_c, auto s1_c, auto ks_c, const void* wf, int t0, f32x16 (&acc)[2][decltype(ntile_c)::value], int tstep = 1) {
     constexpr int NTILE = decltype(ntile_c)::value, DEPTH = decltype(depth_c)::value;
     constexpr int S0 = decltype(s0_c)::value, S1 = decltype(s1_c)::value, KS = decltype(ks_c)::value;
     constexpr int NSTEP = S1 - S0;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(NT) void enc_layer64_kernel(const OppEncChain a) {
       for (int j = 0; j < NTILE; ++j)
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          bq[slot][j][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (((t0 + j) * KS + S0 + s) * 3 + p) * 1024, 0);
+          bq[slot][j][p] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, (((t0 + j * tstep) * KS + S0 + s) * 3 + p) * 1024, 0);
     };
     auto load_a = [&](int s, int slot) {
 #pragma unroll
@@ -331,39 +333,104 @@ __global__ __launch_bounds__(NT) void enc_layer64_kernel(const OppEncChain a) {
   }
   if (!fold) return;
 
-  // ---- 7. the NEXT layer's q | k | v projection of this tile (transformer.py:76-79 of layer i + 1; r05): 24 column tiles of 32, three per
-  //         wave, K = 256; same six-product sequence and epilogue arithmetic as the stand-alone GEMM (gemm_mfma.hip, OPP_ACT_QKV) ---------
+  // ---- 7. the NEXT layer's q | k | v projection of this tile (transformer.py:76-79 of layer i + 1; r05): 24 column tiles of 32, K = 256;
+  //         same six-product sequence and epilogue arithmetic as the stand-alone GEMM (gemm_mfma.hip, OPP_ACT_QKV).  Wave h computes the
+  //         three tiles of HEAD h -- Q tile h, K tile 8 + h, V tile 16 + h -- so the head's phi(K) and V / S of the tile's 64 tokens sit in
+  //         one wave's accumulators and its share of KV_h = sum phi(K)^T V, Ksum_h (linear_attention.py:57-58) is formed right there ------
   float* qdst = (stream && a.qkv_out1 != nullptr) ? a.qkv_out1 + (size_t)(cidx * R64) * (3 * C) : a.qkv_out + (size_t)row0 * (3 * C);
   const float vdiv = (float)seg_len;                  // values / v_length of the stream that produces them (linear_attention.py:55-56)
+  // accumulators -> phi(q) | phi(k) | v / S in place; the rows behind the tile's end become 0 (what the KV reduction reads there)
+  auto finish_qkv = [&](f32x16& t, int rb, bool qk) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = rb + (r & 3) + 8 * (r >> 2) + 4 * half;
+      float v = 0.f;
+      if (row < nrows) {
+        v = t[r];
+        if (qk) v = v > 0.f ? v + 1.f : __expf(v);      // elu(x) + 1, linear_attention.py:10-11
+        else v = v / vdiv;
+        if (stream == 0 && a.qmask != nullptr) v *= a.qmask[row0 + row];   // padded image tokens: q, k, v rows -> 0 (linear_attention.py:49-53)
+      }
+      t[r] = v;
+    }
+  };
   auto store_qkv = [&](const f32x16& t, int rb, int tile) {
     const int col = tile * 32 + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = rb + (r & 3) + 8 * (r >> 2) + 4 * half;
-      if (row < nrows) {
-        float v = t[r];
-        if (col < 2 * C) v = v > 0.f ? v + 1.f : __expf(v);      // elu(x) + 1, linear_attention.py:10-11
-        else v = v / vdiv;
-        if (stream == 0 && a.qmask != nullptr) v *= a.qmask[row0 + row];   // padded image tokens: q, k, v rows -> 0 (linear_attention.py:49-53)
-        qdst[(size_t)row * (3 * C) + col] = v;
-      }
+      if (row < nrows) qdst[(size_t)row * (3 * C) + col] = t[r];
     }
   };
-  {
-    f32x16 acc[2][2];
-    zero2(acc);
-    gemm(I2{}, I3{}, I0{}, I16{}, I16{}, a.wq_next, wave * 3, acc);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) store_qkv(acc[i][j], i * 32, wave * 3 + j);
-  }
+  const bool kv_fold = a.kv_part != nullptr;          // (kernel argument: uniform)
   {
     f32x16 acc[2][1];
     zero2(acc);
-    gemm(I1{}, I4{}, I0{}, I16{}, I16{}, a.wq_next, wave * 3 + 2, acc);
+    gemm(I1{}, I4{}, I0{}, I16{}, I16{}, a.wq_next, h, acc);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) store_qkv(acc[i][0], i * 32, wave * 3 + 2);
+    for (int i = 0; i < 2; ++i) {
+      finish_qkv(acc[i][0], i * 32, true);
+      store_qkv(acc[i][0], i * 32, h);
+    }
+  }
+  f32x16 acc[2][2];                                   // [row block][0: phi(K), 1: V / S] of head h
+  zero2(acc);
+  gemm(I2{}, I3{}, I0{}, I16{}, I16{}, a.wq_next, NW + h, acc, NW);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    finish_qkv(acc[i][0], i * 32, true);
+    finish_qkv(acc[i][1], i * 32, false);
+  }
+  if (!kv_fold) {                                     // the stand-alone reduction (linattn_kv_mfma_kernel) reads K | V from memory
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      store_qkv(acc[i][0], i * 32, NW + h);
+      store_qkv(acc[i][1], i * 32, 2 * NW + h);
+    }
+    return;
+  }
+  // ---- 8. KV / Ksum partial of this 64-token chunk, head h: the chain of linattn_kv_mfma_kernel (attention.hip) on the same operands --
+  //         mfma_32x32x2f32(A = phi(K), B = V / S) over token pairs (2 m, 2 m + 1), m ascending, lane half <-> token parity; Ksum per lane
+  //         in the same order, the two halves added last.  The accumulators hold token (r & 3) + 8 (r >> 2) + 4 half of a 32-row block in
+  //         register r: registers (4 q + 2 e, 4 q + 2 e + 1) of half g are the pair m = 4 q + 2 g + e, and one v_permlane32_swap of the
+  //         two registers hands back the operands of g = 0 (first result) and g = 1 (second): K and V never leave the registers.
+  {
+    f32x16 kvacc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) kvacc[r] = 0.f;
+    float ksum = 0.f;
+    auto swap = [](float x, float y, float& lo, float& hi) {
+      const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x), __builtin_bit_cast(unsigned, y), false, false);
+      lo = __builtin_bit_cast(float, (unsigned)r[0]);
+      hi = __builtin_bit_cast(float, (unsigned)r[1]);
+    };
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float kk[2][2], vv[2][2];                     // [g][e]
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          swap(acc[i][0][4 * q + 2 * e], acc[i][0][4 * q + 2 * e + 1], kk[0][e], kk[1][e]);
+          swap(acc[i][1][4 * q + 2 * e], acc[i][1][4 * q + 2 * e + 1], vv[0][e], vv[1][e]);
+        }
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {
+            kvacc = __builtin_amdgcn_mfma_f32_32x32x2f32(kk[g][e], vv[g][e], kvacc, 0, 0, 0);
+            ksum += kk[g][e];
+          }
+      }
+    // one partial per tile = chunk blockIdx.x of [stream 0 chunks ; stream 1 chunks]: kv_part [chunk][h][d][v], ks_part [chunk][h * 32 + d]
+    float* kvp = a.kv_part + (size_t)blockIdx.x * (C * D) + h * (D * D);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int d = (r & 3) + 8 * (r >> 2) + 4 * half;
+      kvp[d * D + l31] = kvacc[r];
+    }
+    const float tot = ksum + __shfl_xor(ksum, 32, 64);
+    if (half == 0) a.ks_part[(size_t)blockIdx.x * C + h * D + l31] = tot;
   }
 }
 
@@ -377,6 +444,8 @@ int opp_enc_layer64(const OppEncChain& a, hipStream_t stream) {
   OPP_CHECK_ARG(al16(a.X) && al16(a.out) && al16(a.q) && a.ldx % 4 == 0 && a.ldo % 4 == 0 && a.ldq % 4 == 0 && al16(a.g1) && al16(a.b1) &&
                     al16(a.g2) && al16(a.b2) && al16(a.wm) && al16(a.w1) && al16(a.w2) && al16(a.q1), "enc_layer64: operands must be 16-byte aligned");
   OPP_CHECK_ARG(a.wq_next == nullptr || (a.qkv_out != nullptr && al16(a.wq_next)), "enc_layer64: folded projection needs its output buffer");
+  OPP_CHECK_ARG((a.kv_part == nullptr) == (a.ks_part == nullptr) && (a.kv_part == nullptr || (a.wq_next != nullptr && a.qkv_out1 == nullptr)),
+                "enc_layer64: the KV partials need the folded projection and both of their buffers");
   static OppLdsOnce lds_once;            // per device (opp_common.h)
   opp_lds_opt_in(reinterpret_cast<const void*>(enc_layer64_kernel), kLds64, lds_once);
   const int tiles = opp_cdiv(a.len0, R64) + opp_cdiv(a.len1, R64);

@@ -49,6 +49,10 @@ int opp_linattn_apply(const float* q, int ldq, const float* kv, const float* ks,
 size_t opp_linattn_pair_scratch_floats(int len0, int len1);
 int opp_linattn_kv_pair(const float* qkv, int ld, int len0, int len1, float* kv, float* ks, float* scratch,
                         hipStream_t stream);
+// the same kv / ks from one partial per 64-token chunk, which the fused layer kernel wrote into `scratch` (OppEncChain::kv_part / ks_part,
+// placed by opp_linattn_chunk_parts; scratch holds opp_linattn_pair_scratch_floats(len0, len1) floats): the reduce launch alone
+void opp_linattn_chunk_parts(float* scratch, int len0, int len1, float** kv_part, float** ks_part);
+int opp_linattn_reduce_chunks(int len0, int len1, float* kv, float* ks, float* scratch, hipStream_t stream);
 // coarse focal loss of the training step (loss.hip)
 size_t opp_focal_loss_ws_bytes(size_t n);
 int opp_focal_loss_fwd(const float* conf, const short* gt, const float* weight, size_t n, float alpha, float gamma, double* sums,
@@ -105,6 +109,11 @@ struct OppEncChain {
   float* qkv_out = nullptr;
   float* qkv_out1 = nullptr;
   const float* qmask = nullptr;
+  // ... and, with the projection folded, optionally the KV / Ksum partial of every 64-token tile = chunk of the NEXT layer's reduction
+  // (linear_attention.py:57-58), formed from the phi(K) | V / S accumulators: kv_part [chunks0 + chunks1][8][32][32], ks_part [same][256]
+  // (opp_linattn_chunk_parts); the K | V columns of qkv_out are then NOT written -- opp_linattn_reduce_chunks is their only reader
+  float* kv_part = nullptr;
+  float* ks_part = nullptr;
   int cross = 0;
   float eps_attn = 1e-6f;
   // fragment-major bf16x3 weights (opp_pack_frag_b3): merge [C][C], mlp.0 [2C][2C], mlp.2 [C][2C]
