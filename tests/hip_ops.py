@@ -223,7 +223,24 @@ def backbone(model, img):
     return from_nhwc(fc, 256), from_nhwc(ff, 128)
 
 
-def coarse_tokens(model, feat_c_nchw, pe_tokens, kpts, bank_c):
+def _set_state(lib, ctx, mask=None, extent_ref=None):
+    """Per-sample state of the context (include/opp_hip.h: opp_set_query_mask, opp_set_keypoint_extent_ref) from CPU tensors.
+    -> the device tensors, to be kept alive until the call has run; `_clear_state` belongs in the caller's `finally`."""
+    m = mask.float().cuda().contiguous() if mask is not None else None
+    e = extent_ref.float().cuda().contiguous() if extent_ref is not None else None
+    _lib.check(lib.opp_set_query_mask(ctx, m.data_ptr() if m is not None else None), "query_mask")
+    _lib.check(lib.opp_set_keypoint_extent_ref(ctx, e.data_ptr() if e is not None else None, e.shape[0] if e is not None else 0),
+               "extent_ref")
+    return m, e
+
+
+def _clear_state(lib, ctx):
+    lib.opp_set_query_mask(ctx, None)
+    lib.opp_set_keypoint_extent_ref(ctx, None, 0)
+
+
+def coarse_tokens(model, feat_c_nchw, pe_tokens, kpts, bank_c, extent_ref=None):
+    """extent_ref: optional keypoints [n0, 3] of batch element 0 (B > 1: their bounding box scales this cloud, quirk q4)"""
     lib, ctx = ctx_of(model)
     hc, wc = feat_c_nchw.shape[2:]
     L = hc * wc
@@ -234,24 +251,54 @@ def coarse_tokens(model, feat_c_nchw, pe_tokens, kpts, bank_c):
     pe = pe_tokens.cuda().contiguous() if pe_tokens is not None else None
     k = kpts.cuda().contiguous()
     b = bank_c.cuda().contiguous()
-    _lib.check(lib.opp_coarse_tokens(ctx, fc.data_ptr(), pe.data_ptr() if pe is not None else None, L, k.data_ptr(),
-                                     b.data_ptr(), N, tok.data_ptr(), ws.data_ptr(), ws.numel(), _s()), "coarse_tokens")
-    torch.cuda.synchronize()
+    try:
+        keep = _set_state(lib, ctx, None, extent_ref)
+        _lib.check(lib.opp_coarse_tokens(ctx, fc.data_ptr(), pe.data_ptr() if pe is not None else None, L, k.data_ptr(),
+                                         b.data_ptr(), N, tok.data_ptr(), ws.data_ptr(), ws.numel(), _s()), "coarse_tokens")
+        torch.cuda.synchronize()
+    finally:
+        _clear_state(lib, ctx)
+    del keep
     return tok.cpu()
 
 
-def transformer(model, which, tokens, n_seg, len0, len1):
+def encode_points(model, kpts, bank_c, extent_ref=None):
+    """kpts [1, N, 3], bank_c [1, C, N] (cpu) -> the 3D-point tokens [N, C] (opp_encode_points); extent_ref as in coarse_tokens."""
+    lib, ctx = ctx_of(model)
+    N = kpts.shape[1]
+    tok = torch.full((N, bank_c.shape[1]), float("nan"), device="cuda")
+    ws = torch.empty(4096, dtype=torch.uint8, device="cuda")
+    k = kpts.cuda().contiguous()
+    b = bank_c.cuda().contiguous()
+    try:
+        keep = _set_state(lib, ctx, None, extent_ref)
+        _lib.check(lib.opp_encode_points(ctx, k.data_ptr(), b.data_ptr(), N, tok.data_ptr(), ws.data_ptr(), ws.numel(), _s()),
+                   "encode_points")
+        torch.cuda.synchronize()
+    finally:
+        _clear_state(lib, ctx)
+    del keep
+    return tok.cpu()
+
+
+def transformer(model, which, tokens, n_seg, len0, len1, mask=None):
+    """mask: optional CPU floats [len0] (1 = valid image cell, 0 = padding): query_image_mask of the sample (which = 0, n_seg = 1)"""
     lib, ctx = ctx_of(model)
     x = tokens.cuda().contiguous().clone()
     n = lib.opp_transformer_workspace_bytes(ctx, which, n_seg, len0, len1)
     ws = torch.empty(n, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_transformer(ctx, which, x.data_ptr(), n_seg, len0, len1, ws.data_ptr(), n, _s()), "transformer")
-    torch.cuda.synchronize()
+    try:
+        keep = _set_state(lib, ctx, mask, None)
+        _lib.check(lib.opp_transformer(ctx, which, x.data_ptr(), n_seg, len0, len1, ws.data_ptr(), n, _s()), "transformer")
+        torch.cuda.synchronize()
+    finally:
+        _clear_state(lib, ctx)
+    del keep
     return x.cpu()
 
 
-def coarse_match(model, f3d, f2d, hw_c, kpts, base_scale, qscale):
-    """f3d [N,C], f2d [L,C] -> dict like the reference data updates."""
+def coarse_match(model, f3d, f2d, hw_c, kpts, base_scale, qscale, mask=None):
+    """f3d [N,C], f2d [L,C] -> dict like the reference data updates.  mask: optional CPU floats [L], as in `transformer`."""
     lib, ctx = ctx_of(model)
     N, L = f3d.shape[0], f2d.shape[0]
     a, b, k = f3d.cuda().contiguous(), f2d.cuda().contiguous(), kpts.cuda().contiguous()
@@ -265,11 +312,16 @@ def coarse_match(model, f3d, f2d, hw_c, kpts, base_scale, qscale):
     cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
     n = lib.opp_coarse_match_workspace_bytes(ctx, N, L)
     ws = torch.empty(n, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_coarse_match(ctx, a.data_ptr(), b.data_ptr(), N, hw_c[0], hw_c[1], k.data_ptr(), base_scale,
-                                    q.data_ptr() if q is not None else None, conf.data_ptr(), i_ids.data_ptr(),
-                                    j_ids.data_ptr(), mconf.data_ptr(), mkc.data_ptr(), mk3.data_ptr(), cnt.data_ptr(),
-                                    ws.data_ptr(), n, _s()), "coarse_match")
-    torch.cuda.synchronize()
+    try:
+        keep = _set_state(lib, ctx, mask, None)
+        _lib.check(lib.opp_coarse_match(ctx, a.data_ptr(), b.data_ptr(), N, hw_c[0], hw_c[1], k.data_ptr(), base_scale,
+                                        q.data_ptr() if q is not None else None, conf.data_ptr(), i_ids.data_ptr(),
+                                        j_ids.data_ptr(), mconf.data_ptr(), mkc.data_ptr(), mk3.data_ptr(), cnt.data_ptr(),
+                                        ws.data_ptr(), n, _s()), "coarse_match")
+        torch.cuda.synchronize()
+    finally:
+        _clear_state(lib, ctx)
+    del keep
     M = int(cnt.item())
     bz = torch.zeros(M, dtype=torch.int64)
     return {"conf_matrix": conf.cpu(), "b_ids": bz, "i_ids": i_ids[:M].cpu(), "j_ids": j_ids[:M].cpu(),
