@@ -1578,89 +1578,121 @@ int encoder_tail_dense(const EncLayerDesc& e, float* X, const TrBufs& b, int T, 
   return opp_layernorm(b.mrg, C, e.g2, e.b2, X, C, X, C, T, C, eps_ln, s);                          // x + norm2 (:92-94)
 }
 
-// LocalFeatureTransformer.forward with FullAttention layers (transformer.py:32-40: `attention` != "linear"): per layer the plain q / k / v
-// projections of both streams in one GEMM (transformer.py:76-78, no feature map, no V / S), softmax attention into b.msg
-// (csrc/full_attention.hip), then the unchanged merge / norm1 / MLP / norm2 / residual tail -- one fused launch per layer where the linear
-// path has one behind a given message (opp_enc_chain, apply = 0), the dense GEMMs otherwise.  None of the kernels that apply LINEAR attention
-// inside the layer (fold path, chain apply, opp_enc_layer64) runs here.
-int transformer_full_impl(const std::vector<EncLayerDesc>& layers, const int* is_cross, int C, int nhead, float* X, int n_seg, int len0,
-                          int len1, Arena& a, hipStream_t s, int h2, int fusion) {
-  const int D = C / nhead;
-  const int T = n_seg * (len0 + len1);
-  if (T == 0 || layers.empty()) return OPP_OK;
-  OPP_CHECK_ARG(h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3, "transformer: full attention runs in fp32 or bf16x3");
-  OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: full attention needs both token streams");
-  TrBufs b;
-  plan_transformer(C, D, n_seg, len0, len1, a, b);
-  if (!a.ok) {
-    opp_set_error("transformer: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  const float eps_ln = 1e-5f;
-  static const int fuse_env = getenv("OPP_FUSE_LN") ? atoi(getenv("OPP_FUSE_LN")) : 1;   // tuning knob
-  const bool fuse_ln = fuse_env && (C == 256 || C == 128);
-  for (size_t li = 0; li < layers.size(); ++li) {
-    const EncLayerDesc& e = layers[li];
-    OppGemm g;
-    g.nonfinite = t_status_flag;
-    g.tile_policy = t_tile_policy;
-    g.A0 = X;
-    g.lda0 = C;
-    g.ksplit = C;
-    g.W = e.wqkv;
-    g.ldw = (int)split_floats((size_t)C, h2);
-    g.M = T;
-    g.N = 3 * C;
-    g.K = C;
-    g.C = b.qkv;
-    g.ldc = 3 * C;
-    g.n_store = 3 * C;
-    g.act = OPP_ACT_NONE;
-    g.prec = h2;
-    OPP_TRY(opp_gemm_launch(g, s));
-    OPP_TRY(opp_full_attention_run(b.qkv, n_seg, len0, len1, C, nhead, is_cross[li] != 0, h2, b.msg, s));
-    if (fusion && h2 == OPP_PREC_BF16X3 && e.fmerge && opp_enc_chain_ok(C, nhead, false)) {
-      OppEncChain ch;
-      ch.C = C;
-      ch.X = X;
-      ch.ldx = C;
-      ch.out = X;
-      ch.ldo = C;
-      ch.len0 = T;
-      ch.len1 = 0;
-      ch.msg = b.msg;
-      ch.ldm = C;
-      ch.apply = 0;
-      ch.wm = e.fmerge;
-      ch.w1 = e.f1;
-      ch.w2 = e.f2;
-      ch.g1 = e.g1;
-      ch.b1 = e.b1;
-      ch.g2 = e.g2;
-      ch.b2 = e.b2;
-      ch.eps_ln = eps_ln;
-      OPP_TRY(opp_enc_chain(ch, s));
-      continue;
-    }
-    OPP_TRY(encoder_tail_dense(e, X, b, T, C, fuse_ln, eps_ln, s, h2));
-  }
-  return OPP_OK;
+// One of the model's two transformers as the walker sees it: loftr_coarse (which == 0) or loftr_fine
+struct EncLevel {
+  const std::vector<EncLayerDesc>& layers;
+  const int* is_cross;
+  int C, nhead;
+  bool full;                     // FullAttention layers (transformer.py:32-40: `attention` != "linear")
+  int D() const { return C / nhead; }
+};
+EncLevel level_of(const opp_ctx* c, int which) {
+  const opp_config& f = c->cfg;
+  if (which == 0) return {c->coarse, f.coarse_is_cross, f.coarse_d_model, f.coarse_nhead, f.coarse_attention != 0};
+  return {c->fine, f.fine_is_cross, f.fine_d_model, f.fine_nhead, f.fine_attention != 0};
 }
 
-// LocalFeatureTransformer.forward (transformer.py:133-171) on X = [stream0 ; stream1]
+// what a transformer_impl call sets beyond the level and the token shape; call sites name what they set (as ConvOpts).  `fusion` has no
+// default on purpose: every caller names opp_config.encoder_fusion
+struct TrOpts {
+  const float* mask0 = nullptr;          // query_image_mask over the image tokens (stream 0) of a linear level, or null
+  int fusion;                            // opp_config.encoder_fusion: 0 dense GEMMs, 1 one 32-token kernel behind the projection, 2 64-token tiles
+  int prefix_mode = OPP_PREFIX_NONE;     // OPP_PREFIX_*, with `pre` the blob to read (USE) or fill (MAKE)
+  const ObjPrefix* pre = nullptr;
+};
+
+// The A/B switches of the walk (tools and tests; all on by default).  OPP_FUSE_LN=0: LayerNorms of the dense tail as their own launches;
+// OPP_QKV_FOLD=0: every layer launches its projection GEMM; OPP_KV_FOLD=0: every layer launches the stand-alone KV gather -- read on
+// every call, tests/test_kv_fold_gpu.py flips it inside one process
+struct EncSwitches {
+  bool fuse_ln, qkv_fold, kv_fold;
+};
+bool env_is_0(const char* name) {
+  const char* v = getenv(name);
+  return v && v[0] == '0';
+}
+EncSwitches enc_switches() {
+  static const char* const fuse = getenv("OPP_FUSE_LN");
+  static const bool fuse_ln = fuse ? atoi(fuse) != 0 : true, qkv_fold = !env_is_0("OPP_QKV_FOLD");
+  return {fuse_ln, qkv_fold, !env_is_0("OPP_KV_FOLD")};
+}
+
+// The q | k | v projection of one encoder layer (transformer.py:76-78) on the first n_seg * (len0 + l1_qkv) rows of X, both streams in one
+// GEMM, into dst [rows][3 C].  Linear attention: phi(q), phi(k), v / S and the query mask in the epilogue (:79, linear_attention.py:49-53);
+// full attention: the plain projections
+OppGemm qkv_gemm(const EncLayerDesc& e, bool full, const float* X, int C, int n_seg, int len0, int len1, int l1_qkv, const float* mask0,
+                 float* dst, int h2) {
+  const int T0 = n_seg * len0;
+  OppGemm g;
+  g.nonfinite = t_status_flag;
+  g.tile_policy = t_tile_policy;
+  g.A0 = X;
+  g.lda0 = C;
+  g.ksplit = C;
+  g.W = e.wqkv;
+  g.ldw = (int)split_floats((size_t)C, h2);
+  g.M = T0 + n_seg * l1_qkv;
+  g.N = 3 * C;
+  g.K = C;
+  g.C = dst;
+  g.ldc = 3 * C;
+  g.n_store = 3 * C;
+  g.prec = h2;
+  if (full) return g;
+  g.act = OPP_ACT_QKV;
+  g.qk_cols = 2 * C;
+  g.split_row = T0;
+  g.s0 = (float)len0;
+  g.s1 = (float)len1;
+  g.row_mask = mask0;
+  g.row_mask_rows = T0;
+  g.h2_inv = (h2 == OPP_PREC_FP16X2 && e.sqkv) ? e.sqkv + 1 : nullptr;
+  return g;
+}
+
+// what every fused launch behind the projection shares: in place on X, the message buffer, the layer's fragment-major weights and LayerNorms
+OppEncChain enc_chain_of(const EncLayerDesc& e, float* X, int C, const float* msg, float eps_ln) {
+  OppEncChain ch;
+  ch.C = C;
+  ch.X = X;
+  ch.ldx = C;
+  ch.out = X;
+  ch.ldo = C;
+  ch.msg = msg;
+  ch.ldm = C;
+  ch.wm = e.fmerge;
+  ch.w1 = e.f1;
+  ch.w2 = e.f2;
+  ch.g1 = e.g1;
+  ch.b1 = e.b1;
+  ch.g2 = e.g2;
+  ch.b2 = e.b2;
+  ch.eps_ln = eps_ln;
+  return ch;
+}
+
+// LocalFeatureTransformer.forward (transformer.py:133-171) on X = [stream0 ; stream1], in place: per layer the projection, the attention and
+// the merge / norm1 / MLP / norm2 / residual tail.  A full-attention level (csrc/full_attention.hip) is the same walk with the plain
+// projection, softmax attention into b.msg and a tail that is handed the message: none of the kernels that apply LINEAR attention inside
+// the layer (QKV fold, KV partials, opp_enc_layer64), no prefix and no query mask (the callers refuse one).
 // prefix_mode OPP_PREFIX_USE: X's stream-1 rows already hold ObjPrefix::x1; layer 0 then runs on stream 0 only and layer 1 projects /
 // reduces stream 0 only (the 3D stream's share comes from `pre`).  OPP_PREFIX_MAKE (len0 = 0): layer 0 on the 3D stream, then the
 // layer-1 projection and KV / Ksum of that stream into `pre`, and stop.  Rows are independent in every kernel of a layer and the
 // chunking of the KV reduction is per stream, so both modes reproduce the bits of the full evaluation.
-int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cross, int C, int nhead, float* X, int n_seg,
-                     int len0, int len1, Arena& a, hipStream_t s, int h2, const float* mask0 = nullptr, int fusion = 1,
-                     int prefix_mode = OPP_PREFIX_NONE, const ObjPrefix* pre = nullptr) {
-  const int D = C / nhead;
-  const int T0 = n_seg * len0, T1 = n_seg * len1, T = T0 + T1;
+int transformer_impl(const EncLevel& lv, float* X, int n_seg, int len0, int len1, Arena& a, hipStream_t s, int h2, const TrOpts& o) {
+  const std::vector<EncLayerDesc>& layers = lv.layers;
+  const int C = lv.C, D = lv.D();
+  const int T = n_seg * (len0 + len1);
+  const ObjPrefix* pre = o.pre;
   if (T == 0 || layers.empty()) return OPP_OK;
-  if (prefix_mode != OPP_PREFIX_NONE)
-    OPP_CHECK_ARG(pre && n_seg == 1 && C == 256 && D == 32 && fusion == 2 && h2 == OPP_PREC_BF16X3 && layers.size() >= 2 && !is_cross[0] && is_cross[1] &&
-                      (prefix_mode == OPP_PREFIX_USE || len0 == 0), "transformer: object prefix on an unsupported configuration");
+  if (lv.full) {
+    OPP_CHECK_ARG(h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3, "transformer: full attention runs in fp32 or bf16x3");
+    OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: full attention needs both token streams");
+  }
+  if (o.prefix_mode != OPP_PREFIX_NONE)
+    OPP_CHECK_ARG(pre && !lv.full && n_seg == 1 && C == 256 && D == 32 && o.fusion == 2 && h2 == OPP_PREC_BF16X3 && layers.size() >= 2 &&
+                      !lv.is_cross[0] && lv.is_cross[1] && (o.prefix_mode == OPP_PREFIX_USE || len0 == 0),
+                  "transformer: object prefix on an unsupported configuration");
   TrBufs b;
   plan_transformer(C, D, n_seg, len0, len1, a, b);
   if (!a.ok) {
@@ -1668,107 +1700,77 @@ int transformer_impl(const std::vector<EncLayerDesc>& layers, const int* is_cros
     return OPP_ERR_WORKSPACE;
   }
   const float eps_attn = 1e-6f, eps_ln = 1e-5f;
-  static const int fuse_env = getenv("OPP_FUSE_LN") ? atoi(getenv("OPP_FUSE_LN")) : 1;   // tuning knob
-  const bool fuse_ln = fuse_env && (C == 256 || C == 128);
-  // OPP_KV_FOLD=0: every layer launches the stand-alone KV gather (A/B switch of the tools and of tests/test_kv_fold_gpu.py, read per call)
-  const bool kv_fold_env = !(getenv("OPP_KV_FOLD") && getenv("OPP_KV_FOLD")[0] == '0');
+  // the path, as far as shape and configuration decide it (what depends on a layer's packed pointers is asked per layer)
+  const EncSwitches sw = enc_switches();
+  const bool fuse_ln = sw.fuse_ln && (C == 256 || C == 128);                  // dense tail: the LayerNorms in the GEMM epilogues
+  const bool chain_apply = !lv.full && n_seg == 1 && C == 256 && D == 32;     // coarse level, linear: MFMA KV reduction, the fused tail applies KV itself
+  const bool fused_ok = o.fusion && h2 == OPP_PREC_BF16X3 && opp_enc_chain_ok(C, lv.nhead, chain_apply);   // everything behind the attention in ONE launch
+  const bool layer64 = fused_ok && chain_apply && o.fusion == 2;              // ... on 64-token tiles: one round at 9096 tokens
+  const bool qkv_fold = sw.qkv_fold && layer64;                               // layer li's kernel also projects for layer li + 1: only layer 0 launches the GEMM
+  // ... and reduces its tile's phi(K)^T V, sum phi(K) for layer li + 1.  The object-prefix builder keeps the gather: its projection rows
+  // are part of the prefix blob
+  const bool kv_fold = sw.kv_fold && qkv_fold && o.prefix_mode != OPP_PREFIX_MAKE;
   bool kv_parts = false;      // the previous layer's kernel left this layer's KV / Ksum chunk partials in b.scratch
   for (size_t li = 0; li < layers.size(); ++li) {
     const EncLayerDesc& e = layers[li];
-    const bool cross = is_cross[li] != 0;
+    const bool cross = lv.is_cross[li] != 0;
     // stream-1 rows this layer projects / reduces (l1_qkv) and updates (l1_lay)
-    const int l1_qkv = (prefix_mode == OPP_PREFIX_USE && li < 2) ? 0 : len1;
-    const int l1_lay = (prefix_mode == OPP_PREFIX_USE && li == 0) ? 0 : len1;
-    const bool make_tail = prefix_mode == OPP_PREFIX_MAKE && li == 1;     // projection + KV of the 3D stream into the prefix, then stop
-    // the fused coarse path folds layer li + 1's projection into layer li's kernel: only layer 0 launches the GEMM
-    static const bool fold_env = !(getenv("OPP_QKV_FOLD") && getenv("OPP_QKV_FOLD")[0] == '0');     // A/B switch of the tools
-    const bool fold_path = fold_env && fusion == 2 && h2 == OPP_PREC_BF16X3 && n_seg == 1 && C == 256 && D == 32 && e.fmerge && e.fqkv;
-    if (!(fold_path && li > 0)) {  // q/k/v projections of both streams in one GEMM; phi(q), phi(k), v / S fused (transformer.py:76-79)
-      OppGemm g;
-      g.nonfinite = t_status_flag;
-      g.tile_policy = t_tile_policy;
-      g.A0 = X;
-      g.lda0 = C;
-      g.ksplit = C;
-      g.W = e.wqkv;
-      g.ldw = (int)split_floats((size_t)C, h2);
-      g.M = T0 + n_seg * l1_qkv;
-      g.N = 3 * C;
-      g.K = C;
-      g.C = make_tail ? pre->qkv1 : b.qkv;
-      g.ldc = 3 * C;
-      g.n_store = 3 * C;
-      g.act = OPP_ACT_QKV;
-      g.qk_cols = 2 * C;
-      g.split_row = T0;
-      g.s0 = (float)len0;
-      g.s1 = (float)len1;
-      g.row_mask = mask0;        // query_image_mask over the image tokens (stream 0), or null
-      g.row_mask_rows = T0;
-      g.prec = h2;
-      g.h2_inv = (h2 == OPP_PREC_FP16X2 && e.sqkv) ? e.sqkv + 1 : nullptr;
-      OPP_TRY(opp_gemm_launch(g, s));
-    }
+    const int l1_qkv = (o.prefix_mode == OPP_PREFIX_USE && li < 2) ? 0 : len1;
+    const int l1_lay = (o.prefix_mode == OPP_PREFIX_USE && li == 0) ? 0 : len1;
+    const bool make_tail = o.prefix_mode == OPP_PREFIX_MAKE && li == 1;     // projection + KV of the 3D stream into the prefix, then stop
+    const bool fused = fused_ok && e.fmerge;
+    const bool fold = qkv_fold && e.fmerge && e.fqkv;
+
+    // projection
+    if (!(fold && li > 0)) OPP_TRY(opp_gemm_launch(qkv_gemm(e, lv.full, X, C, n_seg, len0, len1, l1_qkv, o.mask0, make_tail ? pre->qkv1 : b.qkv, h2), s));
     if (make_tail) {
       OPP_TRY(opp_linattn_kv_pair(pre->qkv1, 3 * C, 0, len1, b.kv, b.ks, b.scratch, s));
       OPP_TRY(copy_f(pre->kv1, b.kv + (size_t)C * D, (size_t)C * D, s));
       return copy_f(pre->ks1, b.ks + C, C, s);
     }
-    // everything behind the projection in ONE launch (bf16x3): [apply ->] merge -> norm1 -> mlp.0 -> ReLU -> mlp.2 -> norm2 -> +x
-    const bool chain_apply = n_seg == 1 && C == 256 && D == 32;     // coarse level: the kernel applies KV itself
-    if (fusion && h2 == OPP_PREC_BF16X3 && e.fmerge && opp_enc_chain_ok(C, nhead, chain_apply)) {
-      if (kv_parts) OPP_TRY(opp_linattn_reduce_chunks(len0, l1_qkv, b.kv, b.ks, b.scratch, s));     // the gather ran inside layer li - 1
-      else OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, l1_qkv, cross, b.kv, b.ks, b.scratch, chain_apply ? nullptr : b.msg, eps_attn, s));
-      kv_parts = false;
-      OppEncChain ch;
-      ch.C = C;
-      ch.X = X;
-      ch.ldx = C;
-      ch.out = X;
-      ch.ldo = C;
-      ch.len0 = chain_apply ? len0 : T;
-      ch.len1 = chain_apply ? l1_lay : 0;
-      if (prefix_mode == OPP_PREFIX_USE && li == 1) {   // the 3D stream's share of this layer comes from the object prefix
-        ch.q1 = pre->qkv1;
-        ch.kv1 = pre->kv1;
-        ch.ks1 = pre->ks1;
-      }
-      if (fold_path && li + 1 < layers.size() && layers[li + 1].fqkv) {   // this kernel also projects its output rows for layer li + 1
-        ch.wq_next = layers[li + 1].fqkv;
-        ch.qkv_out = b.qkv;
-        ch.qkv_out1 = (prefix_mode == OPP_PREFIX_MAKE && li == 0) ? pre->qkv1 : nullptr;
-        ch.qmask = mask0;
-        // ... and reduces its tile's phi(K)^T V, sum phi(K) for layer li + 1 (the rows layer li + 1 reduces are the rows this launch
-        // projects).  The object-prefix builder keeps the gather: its projection rows are part of the prefix blob
-        const int l1_next = (prefix_mode == OPP_PREFIX_USE && li + 1 < 2) ? 0 : len1;
-        if (kv_fold_env && chain_apply && fusion == 2 && prefix_mode != OPP_PREFIX_MAKE && layers[li + 1].fmerge && ch.len1 == l1_next) {
-          opp_linattn_chunk_parts(b.scratch, ch.len0, ch.len1, &ch.kv_part, &ch.ks_part);
-          kv_parts = true;
-        }
-      }
-      ch.msg = b.msg;
-      ch.ldm = C;
-      ch.apply = chain_apply ? 1 : 0;
+
+    // attention: the message into b.msg, or (chain_apply behind a fused tail) KV / Ksum for the tail to apply
+    if (lv.full) OPP_TRY(opp_full_attention_run(b.qkv, n_seg, len0, len1, C, lv.nhead, cross, h2, b.msg, s));
+    else if (!fused) OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, len1, cross, b.kv, b.ks, b.scratch, b.msg, eps_attn, s));
+    else if (kv_parts) OPP_TRY(opp_linattn_reduce_chunks(len0, l1_qkv, b.kv, b.ks, b.scratch, s));     // the gather ran inside layer li - 1
+    else OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, l1_qkv, cross, b.kv, b.ks, b.scratch, chain_apply ? nullptr : b.msg, eps_attn, s));
+    kv_parts = false;
+
+    // tail: [apply ->] merge -> norm1 -> mlp.0 -> ReLU -> mlp.2 -> norm2 -> +x
+    if (!fused) {
+      OPP_TRY(encoder_tail_dense(e, X, b, T, C, fuse_ln, eps_ln, s, h2));
+      continue;
+    }
+    OppEncChain ch = enc_chain_of(e, X, C, b.msg, eps_ln);
+    ch.len0 = chain_apply ? len0 : T;
+    ch.len1 = chain_apply ? l1_lay : 0;
+    ch.apply = chain_apply ? 1 : 0;
+    if (!lv.full) {
       ch.q = b.qkv;
       ch.ldq = 3 * C;
       ch.kv = b.kv;
       ch.ks = b.ks;
       ch.cross = cross ? 1 : 0;
       ch.eps_attn = eps_attn;
-      ch.wm = e.fmerge;
-      ch.w1 = e.f1;
-      ch.w2 = e.f2;
-      ch.g1 = e.g1;
-      ch.b1 = e.b1;
-      ch.g2 = e.g2;
-      ch.b2 = e.b2;
-      ch.eps_ln = eps_ln;
-      if (chain_apply && fusion == 2) OPP_TRY(opp_enc_layer64(ch, s));   // 64-token tiles: one round at 9096 tokens
-      else OPP_TRY(opp_enc_chain(ch, s));
-      continue;
     }
-    OPP_TRY(run_linattn(b.qkv, C, D, n_seg, len0, len1, cross, b.kv, b.ks, b.scratch, b.msg, eps_attn, s));
-    OPP_TRY(encoder_tail_dense(e, X, b, T, C, fuse_ln, eps_ln, s, h2));
+    if (o.prefix_mode == OPP_PREFIX_USE && li == 1) {   // the 3D stream's share of this layer comes from the object prefix
+      ch.q1 = pre->qkv1;
+      ch.kv1 = pre->kv1;
+      ch.ks1 = pre->ks1;
+    }
+    if (fold && li + 1 < layers.size() && layers[li + 1].fqkv) {
+      ch.wq_next = layers[li + 1].fqkv;
+      ch.qkv_out = b.qkv;
+      ch.qkv_out1 = (o.prefix_mode == OPP_PREFIX_MAKE && li == 0) ? pre->qkv1 : nullptr;
+      ch.qmask = o.mask0;
+      // the rows layer li + 1 reduces must be the rows this launch projects
+      const int l1_next = (o.prefix_mode == OPP_PREFIX_USE && li + 1 < 2) ? 0 : len1;
+      if (kv_fold && layers[li + 1].fmerge && ch.len1 == l1_next) {
+        opp_linattn_chunk_parts(b.scratch, ch.len0, ch.len1, &ch.kv_part, &ch.ks_part);
+        kv_parts = true;
+      }
+    }
+    OPP_TRY(layer64 ? opp_enc_layer64(ch, s) : opp_enc_chain(ch, s));
   }
   return OPP_OK;
 }
@@ -1802,8 +1804,8 @@ extern "C" int opp_set_object_prefix(opp_ctx* ctx, const void* prefix, int n_poi
 
 extern "C" size_t opp_object_prefix_bytes(const opp_ctx* ctx, int n_points) {
   if (!ctx || n_points <= 0 || !obj_prefix_ok(ctx)) return 0;     // 0: this configuration evaluates the whole layers per image
-  const int C = ctx->cfg.coarse_d_model;
-  return opp_align(obj_prefix_floats(C, C / ctx->cfg.coarse_nhead, n_points) * sizeof(float));
+  const EncLevel lv = level_of(ctx, 0);
+  return opp_align(obj_prefix_floats(lv.C, lv.D(), n_points) * sizeof(float));
 }
 
 extern "C" size_t opp_object_prefix_workspace_bytes(const opp_ctx* ctx, int n_points) {
@@ -1816,15 +1818,16 @@ extern "C" int opp_object_prefix(opp_ctx* ctx, const float* tokens3d, int n_poin
   FlagScope flag_scope(ctx);
   OPP_CHECK_ARG(ctx && ctx->packed && tokens3d && prefix && ws && n_points > 0, "object_prefix: bad argument");
   OPP_CHECK_ARG(obj_prefix_ok(ctx), "object_prefix: this configuration has no image-independent transformer prefix (opp_object_prefix_bytes == 0)");
-  const int C = ctx->cfg.coarse_d_model, D = C / ctx->cfg.coarse_nhead;
+  const EncLevel lv = level_of(ctx, 0);
+  const int C = lv.C, D = lv.D();
   OPP_CHECK_ARG(prefix_bytes >= obj_prefix_floats(C, D, n_points) * sizeof(float) && (reinterpret_cast<uintptr_t>(prefix) & 15) == 0,
                 "object_prefix: prefix buffer too small or not 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   ObjPrefix pre = obj_prefix_view(static_cast<float*>(prefix), C, D, n_points);
   OPP_TRY(copy_f(pre.x1, tokens3d, (size_t)n_points * C, s));
   Arena a(ws, ws_bytes);
-  return transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, pre.x1, 1, 0, n_points, a, s, gemm_prec(ctx->cfg), nullptr,
-                          ctx->cfg.encoder_fusion, OPP_PREFIX_MAKE, &pre);
+  return transformer_impl(lv, pre.x1, 1, 0, n_points, a, s, gemm_prec(ctx->cfg),
+                          {.fusion = ctx->cfg.encoder_fusion, .prefix_mode = OPP_PREFIX_MAKE, .pre = &pre});
 }
 
 namespace {
@@ -1875,21 +1878,19 @@ extern "C" int opp_full_attention(const float* qkv, int n_seg, int len0, int len
 
 extern "C" size_t opp_transformer_workspace_bytes(const opp_ctx* ctx, int which, int n_seg, int len0, int len1) {
   if (!ctx) return 0;
-  const int C = which == 0 ? ctx->cfg.coarse_d_model : ctx->cfg.fine_d_model;
-  const int nh = which == 0 ? ctx->cfg.coarse_nhead : ctx->cfg.fine_nhead;
+  const EncLevel lv = level_of(ctx, which);
   Arena a(nullptr, 0);
   TrBufs b;
-  return opp_align(plan_transformer(C, C / nh, n_seg, len0, len1, a, b)) + 256;
+  return opp_align(plan_transformer(lv.C, lv.D(), n_seg, len0, len1, a, b)) + 256;
 }
 
 extern "C" int opp_transformer_kv_offsets(const opp_ctx* ctx, int which, int n_seg, int len0, int len1, size_t* kv_offset, size_t* ks_offset) {
   OPP_CHECK_ARG(ctx && kv_offset && ks_offset && (which == 0 || which == 1), "transformer_kv_offsets: bad argument");
-  const int C = which == 0 ? ctx->cfg.coarse_d_model : ctx->cfg.fine_d_model;
-  const int nh = which == 0 ? ctx->cfg.coarse_nhead : ctx->cfg.fine_nhead;
+  const EncLevel lv = level_of(ctx, which);
   char* const base = reinterpret_cast<char*>(uintptr_t(1) << 20);     // never dereferenced: the plan only adds offsets to it
   Arena a(base, ~size_t(0) >> 1);
   TrBufs b;
-  plan_transformer(C, C / nh, n_seg, len0, len1, a, b);
+  plan_transformer(lv.C, lv.D(), n_seg, len0, len1, a, b);
   *kv_offset = (size_t)(reinterpret_cast<char*>(b.kv) - base);
   *ks_offset = (size_t)(reinterpret_cast<char*>(b.ks) - base);
   return OPP_OK;
@@ -1902,20 +1903,12 @@ extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg
   OPP_CHECK_ARG(ctx->tr_packed, "transformer: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(which == 0 || which == 1, "transformer: which must be 0 or 1");
   Arena a(ws, ws_bytes);
-  if (which == 0 && ctx->cfg.coarse_attention) {
+  const EncLevel lv = level_of(ctx, which);
+  if (which == 0 && lv.full)
     OPP_CHECK_ARG(n_seg != 1 || !ctx->query_mask, "transformer: full attention with a query mask is unsupported (upstream FullAttention indexes the "
                                                   "None q_mask of the cross layers, linear_attention.py:84-85)");
-    return transformer_full_impl(ctx->coarse, ctx->cfg.coarse_is_cross, ctx->cfg.coarse_d_model, ctx->cfg.coarse_nhead, tokens, n_seg, len0, len1, a,
-                                 (hipStream_t)stream, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion);
-  }
-  if (which == 1 && ctx->cfg.fine_attention)
-    return transformer_full_impl(ctx->fine, ctx->cfg.fine_is_cross, ctx->cfg.fine_d_model, ctx->cfg.fine_nhead, tokens, n_seg, len0, len1, a,
-                                 (hipStream_t)stream, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion);
-  if (which == 0)
-    return transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, ctx->cfg.coarse_d_model, ctx->cfg.coarse_nhead, tokens, n_seg, len0, len1, a, (hipStream_t)stream, gemm_prec(ctx->cfg),
-                            n_seg == 1 ? ctx->query_mask : nullptr, ctx->cfg.encoder_fusion);
-  return transformer_impl(ctx->fine, ctx->cfg.fine_is_cross, ctx->cfg.fine_d_model, ctx->cfg.fine_nhead, tokens, n_seg, len0, len1, a, (hipStream_t)stream, gemm_prec(ctx->cfg),
-                          nullptr, ctx->cfg.encoder_fusion);
+  return transformer_impl(lv, tokens, n_seg, len0, len1, a, (hipStream_t)stream, gemm_prec(ctx->cfg),
+                          {.mask0 = which == 0 && n_seg == 1 ? ctx->query_mask : nullptr, .fusion = ctx->cfg.encoder_fusion});
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2070,7 +2063,8 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
     return OPP_ERR_WORKSPACE;
   }
   size_t mark = a.off;
-  const int hc = H / 8, wc = W / 8, L = hc * wc, C = ctx->cfg.coarse_d_model;
+  const EncLevel lv = level_of(ctx, 0);
+  const int hc = H / 8, wc = W / 8, L = hc * wc, C = lv.C;
   bool forked = false;
   // what runs beside the coarse level: the whole FPN fine branch (-> feat_f), or -- match-driven fine branch, opp_set_fine_patch_buffers --
   // only its 1/4-resolution half (-> x2_out; x1 / x2_out land in the caller's buffers), or nothing (feat_f = NULL: the fine map is dead)
@@ -2143,15 +2137,13 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   // resident object with a transformer prefix (opp_set_object_prefix): its 3D tokens enter already past layer 0
   const bool use_prefix = ctx->obj_prefix != nullptr && ctx->obj_prefix_n == n && tokens3d_pre != nullptr && obj_prefix_ok(ctx);
   ObjPrefix pre;
-  if (use_prefix) pre = obj_prefix_view(const_cast<float*>(ctx->obj_prefix), C, C / ctx->cfg.coarse_nhead, n);
+  if (use_prefix) pre = obj_prefix_view(const_cast<float*>(ctx->obj_prefix), C, lv.D(), n);
   OPP_TRY(coarse_tokens_impl(ctx, feat_c, ctx->cfg.pos_enc_enable ? pe : nullptr, L, kpts, bank_c, n, use_prefix ? pre.x1 : tokens3d_pre, tokens, a, s));
   a.off = mark;
-  if (ctx->cfg.coarse_attention)   // use_prefix is false here (obj_prefix_ok); the query mask was refused on entry
-    OPP_TRY(transformer_full_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg),
-                                  ctx->cfg.encoder_fusion));
-  else
-    OPP_TRY(transformer_impl(ctx->coarse, ctx->cfg.coarse_is_cross, C, ctx->cfg.coarse_nhead, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg), ctx->query_mask,
-                             ctx->cfg.encoder_fusion, use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE, use_prefix ? &pre : nullptr));
+  // full attention: use_prefix is false (obj_prefix_ok) and the query mask was refused on entry
+  OPP_TRY(transformer_impl(lv, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg),
+                           {.mask0 = ctx->query_mask, .fusion = ctx->cfg.encoder_fusion, .prefix_mode = use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE,
+                            .pre = use_prefix ? &pre : nullptr}));
   a.off = mark;
   return coarse_match_impl(ctx, tokens + (size_t)L * C, tokens, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c,
                            mkpts_3d, count, a, s);
@@ -2166,10 +2158,7 @@ int fine_tail(opp_ctx* ctx, float* X, int M, const float* mkpts_c, float base_sc
               float* mkpts_f, Arena& a, hipStream_t s) {
   const int C = ctx->cfg.fine_d_model, Wwin = ctx->cfg.fine_window, WW = Wwin * Wwin;
   float* f3 = X + (size_t)M * WW * C;
-  if (run_transformer && ctx->cfg.fine_attention)
-    OPP_TRY(transformer_full_impl(ctx->fine, ctx->cfg.fine_is_cross, C, ctx->cfg.fine_nhead, X, M, WW, 1, a, s, gemm_prec(ctx->cfg), ctx->cfg.encoder_fusion));
-  else if (run_transformer)
-    OPP_TRY(transformer_impl(ctx->fine, ctx->cfg.fine_is_cross, C, ctx->cfg.fine_nhead, X, M, WW, 1, a, s, gemm_prec(ctx->cfg), nullptr, ctx->cfg.encoder_fusion));
+  if (run_transformer) OPP_TRY(transformer_impl(level_of(ctx, 1), X, M, WW, 1, a, s, gemm_prec(ctx->cfg), {.fusion = ctx->cfg.encoder_fusion}));
   const float temp = (float)(1.0 / sqrt((double)C));   // fine_matching.py:82
   return opp_fine_head(f3, C, X, C, M, Wwin, C, temp, mkpts_c, base_scale, qscale, expec_f, mkpts_f, s);
 }

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from onepose_plus_plus_amd import _lib
+from onepose_plus_plus_amd.synthetic import make_state_dict
 from tests import helpers as H
 from tests.golden.fullattn_cases import (FULLATTN_TRANSFORMER_CASES, FULLATTN_E2E_CASES, FULLATTN_BATCH_CASES, fullattn_transformer_setup,
                                          fullattn_e2e_setup, fullattn_batch_setup, full_config)
@@ -152,3 +153,27 @@ def test_full_attention_object_cache_changes_nothing():
             assert torch.equal(outs[0][k], o[k]), k
     lib, ctx = ops.ctx_of(cached)
     assert lib.opp_object_prefix_bytes(ctx, 300) == 0
+
+
+# (which, n_seg, len0, len1): coarse tiles that end inside a 32-row block and a one-token stream; fine windows, many segments and one
+FUSION_SHAPES = [(0, 1, 96, 77), (0, 1, 65, 129), (0, 1, 31, 1), (1, 37, 25, 1), (1, 1, 25, 1)]
+
+
+@pytest.mark.parametrize("precision", list(PRECISIONS))
+@pytest.mark.parametrize("shape", FUSION_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_full_attention_encoder_fusion_levels_are_bit_identical(shape, precision):
+    """A full-attention layer behind its softmax attention is the dense merge / norm1 / MLP / norm2 GEMMs (encoder_fusion 0) or one
+    fused launch on the given message (1 and 2; bf16x3 only -- fp32 ignores the level): both walk K in the same k16-steps with the
+    same bf16 products, so the whole transformer must agree bit for bit between the three levels, at both levels of the model."""
+    from tests import hip_ops as ops
+    which, n_seg, len0, len1 = shape
+    cfg = full_config(H.default_config())
+    sd = make_state_dict(cfg, 3)
+    g = torch.Generator().manual_seed(11 + len0 + n_seg)
+    tokens = torch.randn(n_seg * (len0 + len1), 256 if which == 0 else 128, generator=g)
+    outs = [ops.transformer(ops.make_model(cfg, sd, precision).set_encoder_fusion(level).cuda(), which, tokens, n_seg, len0, len1)
+            for level in (0, 1, 2)]
+    for level, a in enumerate(outs):
+        assert torch.isfinite(a).all(), level
+        assert not torch.equal(a, tokens), level
+        assert torch.equal(a, outs[0]), "level %d: max |fused - plain| = %.3e" % (level, (a - outs[0]).abs().max().item())

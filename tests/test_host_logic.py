@@ -267,3 +267,31 @@ def test_tape_layout_sizes_are_pinned(shape):
         assert (lib.opp_backbone_tape_bytes(ctx, *shape), lib.opp_backbone_train_tape_workspace_bytes(ctx, *shape)) == TAPE_BYTES[shape]
     finally:
         lib.opp_destroy(ctx)
+
+
+# (which, n_seg, len0, len1) -> opp_transformer_workspace_bytes, kv_offset, ks_offset (opp_transformer_kv_offsets) of the default
+# configuration, recorded from the build of commit 4c7012e.  tests/test_kv_fold_gpu.py reads KV / Ksum at these offsets.
+TRANSFORMER_WS = {(0, 1, 4096, 5000): (70100224, 65200128, 65265664), (0, 1, 96, 77): (1443072, 1240064, 1305600),
+                  (0, 2, 96, 77): (2750720, 2480128, 2611200), (0, 1, 0, 300): (2387200, 2150400, 2215936),
+                  (1, 500, 25, 1): (59648256, 46592000, 54784000), (1, 1, 25, 1): (119552, 93184, 109568)}
+# opp_object_prefix_bytes, opp_object_prefix_workspace_bytes at 5000 points, same build (no weights packed: no prefix, 0 bytes)
+PREFIX_BYTES_N5000 = (0, 38577408)
+
+
+def test_transformer_workspace_layout_is_pinned():
+    """The workspace plan of the encoder walk is host arithmetic shared by opp_transformer, its callers and the tests that read
+    KV / Ksum out of the workspace: sizes and offsets of both levels must not move (one and many segments, an empty stream)."""
+    import ctypes
+    from onepose_plus_plus_amd import _lib
+    lib = _lib.load()
+    ctx = ctypes.c_void_p()
+    ccfg = OnePosePlus_model(default_config())._c_config()
+    _lib.check(lib.opp_create(ctypes.byref(ccfg), ctypes.byref(ctx)), "opp_create")
+    try:
+        for case, pinned in TRANSFORMER_WS.items():
+            kv, ks = ctypes.c_size_t(), ctypes.c_size_t()
+            _lib.check(lib.opp_transformer_kv_offsets(ctx, *case, ctypes.byref(kv), ctypes.byref(ks)), "opp_transformer_kv_offsets")
+            assert (lib.opp_transformer_workspace_bytes(ctx, *case), kv.value, ks.value) == pinned, case
+        assert (lib.opp_object_prefix_bytes(ctx, 5000), lib.opp_object_prefix_workspace_bytes(ctx, 5000)) == PREFIX_BYTES_N5000
+    finally:
+        lib.opp_destroy(ctx)
