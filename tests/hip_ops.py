@@ -329,18 +329,20 @@ def coarse_match(model, f3d, f2d, hw_c, kpts, base_scale, qscale, mask=None):
             "m_bids": bz, "gt_mask": torch.zeros(M, dtype=torch.bool)}
 
 
-def fine(model, feat_f_nchw, bank_f, i_ids, j_ids, hw_c, mkpts_c, base_scale, qscale, run_transformer=1):
+def fine(model, feat_f_nchw, bank_f, i_ids, j_ids, hw_c, mkpts_c, base_scale, qscale, run_transformer=1, spare_rows=0):
+    """-> expec_f [M + spare_rows, 3], mkpts_query_f [M + spare_rows, 2], prefilled with NaN: the call may write the first M rows only
+    (M = 0: an empty match list passes through, nothing is written)"""
     lib, ctx = ctx_of(model)
     hf, wf = feat_f_nchw.shape[2:]
     M = i_ids.numel()
     N = bank_f.shape[2]
     ff = to_nhwc_padded(feat_f_nchw, 128)
     bk = bank_f.cuda().contiguous()
-    ii, jj = i_ids.cuda().contiguous(), j_ids.cuda().contiguous()
-    mk = mkpts_c.cuda().float().contiguous()
+    ii, jj = i_ids.long().cuda().contiguous(), j_ids.long().cuda().contiguous()
+    mk = mkpts_c.cuda().float().reshape(M, 2).contiguous()
     q = qscale.cuda().contiguous() if qscale is not None else None
-    ex = torch.full((M, 3), float("nan"), device="cuda")
-    mf = torch.full((M, 2), float("nan"), device="cuda")
+    ex = torch.full((M + spare_rows, 3), float("nan"), device="cuda")
+    mf = torch.full((M + spare_rows, 2), float("nan"), device="cuda")
     n = lib.opp_fine_workspace_bytes(ctx, M)
     ws = torch.empty(n, dtype=torch.uint8, device="cuda")
     _lib.check(lib.opp_fine(ctx, ff.data_ptr(), hf, wf, bk.data_ptr(), N, ii.data_ptr(), jj.data_ptr(), M, hw_c[0],

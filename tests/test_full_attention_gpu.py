@@ -46,7 +46,8 @@ def _reference(qkv, n_seg, len0, len1, C, nhead, cross):
 
 
 SHAPES = [(1, 4096, 5000, 256, 8), (1, 4096, 15000, 256, 8), (1, 96, 77, 256, 8), (1, 31, 1, 256, 8), (1, 65, 129, 256, 8),
-          (1, 1, 64, 256, 8), (500, 25, 1, 128, 8), (37, 25, 1, 128, 8), (1, 25, 1, 128, 8)]
+          (1, 1, 64, 256, 8), (500, 25, 1, 128, 8), (37, 25, 1, 128, 8), (1, 25, 1, 128, 8), (37, 9, 1, 128, 8),
+          (37, 49, 1, 128, 8)]
 
 
 @pytest.mark.parametrize("sharp", [False, True])

@@ -409,6 +409,8 @@ LINATTN_CASES = [
     (5, 9, 23, 128, 8),
     (3, 100, 40, 128, 8),                  # generic path (chunk partials + fixed-order reduction)
     (2, 640, 300, 256, 8),                 # B > 1 at the coarse level
+    (130, 49, 1, 128, 8),                  # fine level at window 7: 50 tokens per match, the generic path with one segment per match
+    (37, 9, 1, 128, 8),                    # fine level at window 3
 ]
 
 
@@ -464,7 +466,7 @@ def test_linear_attention_vs_fp64(n_seg, len0, len1, C, nhead, cross):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("which,n_seg,len0,len1", [(0, 1, 4096, 5000), (0, 1, 96, 77), (0, 1, 31, 1), (0, 1, 64, 33), (0, 1, 65, 129),
-                                                    (1, 500, 25, 1), (1, 1, 25, 1), (1, 37, 25, 1)])
+                                                    (1, 500, 25, 1), (1, 1, 25, 1), (1, 37, 25, 1), (1, 37, 9, 1), (1, 37, 49, 1)])
 def test_encoder_chain_is_bit_identical_to_the_launch_per_linear_path(which, n_seg, len0, len1):
     """One LoFTREncoderLayer behind its Q/K/V projection as ONE kernel (enc_chain.hip: attention apply, merge, norm1,
     mlp.0, ReLU, mlp.2, norm2, residual on 32-token tiles held in LDS; transformer.py:80-94) against the same layers run
