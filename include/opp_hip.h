@@ -93,6 +93,22 @@ typedef struct opp_config {
    * opp_create refuses other values (OPP_ERR_UNSUPPORTED). */
   int coarse_attention;
   int fine_attention;
+  /* loftr_coarse.norm_method / loftr_fine.norm_method (transformer.py:49-54): 0 = "layernorm" (the default), 1 = "instancenorm" =
+   * nn.InstanceNorm1d(d_model) applied to [N, L, C] tokens = the per-token normalisation over the C channels without affine: the level's
+   * norm1 / norm2 names are not in the weight table, the packed affine slots hold ones and zeros and every layer kernel runs unchanged. */
+  int coarse_norm;
+  int fine_norm;
+  /* loftr_coarse.rezero / loftr_fine.rezero is a number (transformer.py:61-63, :94: x + res_weight * message): 1 = every layer of the level
+   * has a `res_weight` [1] entry in the weight table (in front of q_proj.weight, as in the reference state dict); opp_pack_weights folds it
+   * into the packed norm2 affine (gamma2 * w, beta2 * w), so the residual add of the layer kernels needs no further operand. */
+  int coarse_rezero;
+  int fine_rezero;
+  /* keypoints_encoding.norm_method (position_encoding.py:69-74): 0 = "instancenorm" (per-point normalisation over the channels, no affine;
+   * the default), 1 = "layernorm" (the same normalisation + nn.LayerNorm's affine: encoder.{1,4,7}.{weight,bias} join the weight table). */
+  int kpt_norm;
+  /* coarse_matching.feat_norm_method (coarse_matching.py:46-54): 0 = "sqrt_feat_dim" (scores divided by C; the default), 1 = "none" / None
+   * (scores as they are). */
+  int feat_norm;
 } opp_config;
 
 typedef struct opp_ctx opp_ctx;

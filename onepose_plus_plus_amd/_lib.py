@@ -39,6 +39,12 @@ class OppConfig(Structure):
         ("fpn_overlap", c_int),
         ("coarse_attention", c_int),
         ("fine_attention", c_int),
+        ("coarse_norm", c_int),
+        ("fine_norm", c_int),
+        ("coarse_rezero", c_int),
+        ("fine_rezero", c_int),
+        ("kpt_norm", c_int),
+        ("feat_norm", c_int),
     ]
 
 

@@ -77,7 +77,9 @@ struct BlockDesc {
 };
 
 struct EncLayerDesc {
-  int q_idx = -1;  // q,k,v,merge,mlp0,mlp2,norm1.w,norm1.b,norm2.w,norm2.b follow consecutively
+  int q_idx = -1;  // q,k,v,merge,mlp0,mlp2 follow consecutively
+  int n_idx = -1;  // norm1.w,norm1.b,norm2.w,norm2.b follow consecutively; -1 = norm_method "instancenorm" (no affine in the state dict)
+  int rw_idx = -1; // res_weight [1] of a rezero level, or -1
   float *wqkv = nullptr, *wmerge = nullptr, *w1 = nullptr, *w2 = nullptr;
   float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
   float *sqkv = nullptr, *smerge = nullptr, *s1 = nullptr, *s2 = nullptr;   // fp16x2 {scale, 1/scale} per matrix
@@ -99,6 +101,11 @@ struct opp_ctx {
   int kpt_idx = -1;
   float* kpt_wt[4] = {nullptr, nullptr, nullptr, nullptr};
   float* kpt_b[4] = {nullptr, nullptr, nullptr, nullptr};
+  // keypoints_encoding.norm_method "layernorm": table index of encoder.{1,4,7}.weight (the bias follows) and the packed affine; else -1 / null
+  int kpt_ln_idx[3] = {-1, -1, -1};
+  float* kpt_g[3] = {nullptr, nullptr, nullptr};
+  float* kpt_be[3] = {nullptr, nullptr, nullptr};
+  int kpt_lin_idx[4] = {-1, -1, -1, -1};   // table index of encoder.{0,3,6,9}.weight (the bias follows)
   // transformers
   std::vector<EncLayerDesc> coarse, fine;
   bool packed = false;
@@ -191,20 +198,24 @@ BlockDesc mk_block(opp_ctx* c, const std::string& p, int cin, int cout, int stri
   }
   return b;
 }
-void mk_transformer(opp_ctx* c, const std::string& name, int d, int n_layers, std::vector<EncLayerDesc>& out) {
+// state-dict order of LoFTREncoderLayer: its own parameter (res_weight, rezero only) in front of the sub-modules' (transformer.py:26-62)
+void mk_transformer(opp_ctx* c, const std::string& name, int d, int n_layers, bool instancenorm, bool rezero, std::vector<EncLayerDesc>& out) {
   for (int i = 0; i < n_layers; ++i) {
     const std::string p = name + ".layers." + std::to_string(i);
     EncLayerDesc e;
+    if (rezero) e.rw_idx = add_w(c, p + ".res_weight", 1);
     e.q_idx = add_w(c, p + ".q_proj.weight", (long long)d * d);
     add_w(c, p + ".k_proj.weight", (long long)d * d);
     add_w(c, p + ".v_proj.weight", (long long)d * d);
     add_w(c, p + ".merge.weight", (long long)d * d);
     add_w(c, p + ".mlp.0.weight", (long long)4 * d * d);
     add_w(c, p + ".mlp.2.weight", (long long)2 * d * d);
-    add_w(c, p + ".norm1.weight", d);
-    add_w(c, p + ".norm1.bias", d);
-    add_w(c, p + ".norm2.weight", d);
-    add_w(c, p + ".norm2.bias", d);
+    if (!instancenorm) {   // nn.InstanceNorm1d(d_model): affine = False, no running statistics -> no keys (transformer.py:52-54)
+      e.n_idx = add_w(c, p + ".norm1.weight", d);
+      add_w(c, p + ".norm1.bias", d);
+      add_w(c, p + ".norm2.weight", d);
+      add_w(c, p + ".norm2.bias", d);
+    }
     out.push_back(e);
   }
 }
@@ -262,6 +273,12 @@ extern "C" int opp_create(const opp_config* cfg, opp_ctx** out) {
     opp_set_error("full attention runs in gemm_precision 0 (fp32) or 3 (bf16x3), got %d", cfg->gemm_precision);
     return OPP_ERR_UNSUPPORTED;
   }
+  for (int v : {cfg->coarse_norm, cfg->fine_norm, cfg->coarse_rezero, cfg->fine_rezero, cfg->kpt_norm, cfg->feat_norm}) {
+    if (v != 0 && v != 1) {
+      opp_set_error("coarse_norm / fine_norm / coarse_rezero / fine_rezero / kpt_norm / feat_norm must be 0 or 1, got %d", v);
+      return OPP_ERR_UNSUPPORTED;
+    }
+  }
   opp_ctx* c = new opp_ctx();
   c->cfg = *cfg;
   const int d0 = cfg->initial_dim, d1 = cfg->block_dims[0], d2 = cfg->block_dims[1], d3 = cfg->block_dims[2];
@@ -290,13 +307,18 @@ extern "C" int opp_create(const opp_config* cfg, opp_ctx** out) {
     const int ch[5] = {3, cfg->kpt_enc_dims[0], cfg->kpt_enc_dims[1], cfg->kpt_enc_dims[2], cfg->coarse_d_model};
     for (int i = 0; i < 4; ++i) {
       const std::string p = "kpt_3d_pos_encoding.encoder." + std::to_string(3 * i);
-      const int idx = add_w(c, p + ".weight", (long long)ch[i + 1] * ch[i]);
+      c->kpt_lin_idx[i] = add_w(c, p + ".weight", (long long)ch[i + 1] * ch[i]);
       add_w(c, p + ".bias", ch[i + 1]);
-      if (i == 0) c->kpt_idx = idx;
+      if (cfg->kpt_norm == 1 && i < 3) {   // nn.LayerNorm(channels[i]) behind every hidden Linear (position_encoding.py:71-72)
+        const std::string q = "kpt_3d_pos_encoding.encoder." + std::to_string(3 * i + 1);
+        c->kpt_ln_idx[i] = add_w(c, q + ".weight", ch[i + 1]);
+        add_w(c, q + ".bias", ch[i + 1]);
+      }
     }
+    c->kpt_idx = c->kpt_lin_idx[0];
   }
-  mk_transformer(c, "loftr_coarse", cfg->coarse_d_model, cfg->coarse_n_layers, c->coarse);
-  mk_transformer(c, "loftr_fine", cfg->fine_d_model, cfg->fine_n_layers, c->fine);
+  mk_transformer(c, "loftr_coarse", cfg->coarse_d_model, cfg->coarse_n_layers, cfg->coarse_norm == 1, cfg->coarse_rezero == 1, c->coarse);
+  mk_transformer(c, "loftr_fine", cfg->fine_d_model, cfg->fine_n_layers, cfg->fine_norm == 1, cfg->fine_rezero == 1, c->fine);
   *out = c;
   return OPP_OK;
 }
@@ -390,6 +412,10 @@ size_t plan_pack(opp_ctx* c, void* base) {
       c->kpt_wt[i] = a.f((size_t)ch[i] * ch[i + 1]);
       c->kpt_b[i] = a.f(ch[i + 1]);
     }
+    for (int i = 0; i < 3; ++i) {   // "layernorm" affine only: the default configuration's layout is unchanged
+      c->kpt_g[i] = c->kpt_ln_idx[i] >= 0 ? a.f(ch[i + 1]) : nullptr;
+      c->kpt_be[i] = c->kpt_ln_idx[i] >= 0 ? a.f(ch[i + 1]) : nullptr;
+    }
   }
   auto plan_tr = [&](std::vector<EncLayerDesc>& L, int d) {
     for (auto& e : L) {
@@ -478,8 +504,12 @@ extern "C" int opp_pack_weights(opp_ctx* c, const float* const* w, int n, void* 
     const int ch[5] = {3, c->cfg.kpt_enc_dims[0], c->cfg.kpt_enc_dims[1], c->cfg.kpt_enc_dims[2], c->cfg.coarse_d_model};
     for (int i = 0; i < 4; ++i) {
       // PyTorch Linear weight [Cout][Cin] -> [Cin][Cout]
-      OPP_TRY(opp_transpose(w[c->kpt_idx + 2 * i], c->kpt_wt[i], 1, ch[i + 1], ch[i], s));
-      OPP_TRY(copy_f(c->kpt_b[i], w[c->kpt_idx + 2 * i + 1], ch[i + 1], s));
+      OPP_TRY(opp_transpose(w[c->kpt_lin_idx[i]], c->kpt_wt[i], 1, ch[i + 1], ch[i], s));
+      OPP_TRY(copy_f(c->kpt_b[i], w[c->kpt_lin_idx[i] + 1], ch[i + 1], s));
+      if (i < 3 && c->kpt_ln_idx[i] >= 0) {
+        OPP_TRY(copy_f(c->kpt_g[i], w[c->kpt_ln_idx[i]], ch[i + 1], s));
+        OPP_TRY(copy_f(c->kpt_be[i], w[c->kpt_ln_idx[i] + 1], ch[i + 1], s));
+      }
     }
   }
   auto pack_tr = [&](std::vector<EncLayerDesc>& L, int d) -> int {
@@ -492,10 +522,24 @@ extern "C" int opp_pack_weights(opp_ctx* c, const float* const* w, int n, void* 
       OPP_TRY(copy_f(e.wmerge, w[q + 3], dd, s));
       OPP_TRY(copy_f(e.w1, w[q + 4], 4 * dd, s));
       OPP_TRY(copy_f(e.w2, w[q + 5], 2 * dd, s));
-      OPP_TRY(copy_f(e.g1, w[q + 6], d, s));
-      OPP_TRY(copy_f(e.b1, w[q + 7], d, s));
-      OPP_TRY(copy_f(e.g2, w[q + 8], d, s));
-      OPP_TRY(copy_f(e.b2, w[q + 9], d, s));
+      // norm affine: "instancenorm" = ones / zeros; rezero: x + w (y g2 + b2) = x + y (w g2) + w b2, folded here so that the layer kernels'
+      // residual add needs no further operand (the default configuration keeps its four plain copies)
+      const int nn = e.n_idx;
+      const float* rw = e.rw_idx >= 0 ? w[e.rw_idx] : nullptr;
+      if (nn >= 0) {
+        OPP_TRY(copy_f(e.g1, w[nn], d, s));
+        OPP_TRY(copy_f(e.b1, w[nn + 1], d, s));
+      } else {
+        OPP_TRY(opp_pack_affine(nullptr, 1.0f, nullptr, e.g1, d, s));
+        OPP_TRY(opp_pack_affine(nullptr, 0.0f, nullptr, e.b1, d, s));
+      }
+      if (nn >= 0 && !rw) {
+        OPP_TRY(copy_f(e.g2, w[nn + 2], d, s));
+        OPP_TRY(copy_f(e.b2, w[nn + 3], d, s));
+      } else {
+        OPP_TRY(opp_pack_affine(nn >= 0 ? w[nn + 2] : nullptr, 1.0f, rw, e.g2, d, s));
+        OPP_TRY(opp_pack_affine(nn >= 0 ? w[nn + 3] : nullptr, 0.0f, rw, e.b2, d, s));
+      }
       if (e.fqkv) OPP_TRY(opp_pack_frag_b3(e.wqkv, 3 * d, d, e.fqkv, s));     // (e.wqkv is still the fp32 concatenation here)
       if (e.fmerge) {
         OPP_TRY(opp_pack_frag_b3(w[q + 3], d, d, e.fmerge, s));
@@ -1411,7 +1455,7 @@ int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n
         return OPP_ERR_LAUNCH;
       }
     }
-    return opp_kpt_encode(kpts, stats, bank_c, n, c->kpt_wt, c->kpt_b, t3, C, s);
+    return opp_kpt_encode(kpts, stats, bank_c, n, c->kpt_wt, c->kpt_b, c->kpt_g, c->kpt_be, t3, C, s);
   }
   return opp_bank_transpose(bank_c, n, C, t3, C, s);
 }
@@ -1920,6 +1964,8 @@ int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int h
                       const float* qscale, float* conf, long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c,
                       float* mkpts_3d, int* count, Arena& a, hipStream_t s) {
   const int C = c->cfg.coarse_d_model, L = hc * wc;
+  // coarse_matching.feat_norm_method: "sqrt_feat_dim" divides both token sets by sqrt(C), "none" leaves them (coarse_matching.py:46-50)
+  const float feat_mul = c->cfg.feat_norm == 1 ? 1.0f : 1.0f / (float)C;
   float* scratch = a.f(opp_coarse_match_scratch_floats(n, L));
   float* stats = a.f(opp_coarse_match_stats_floats(n, L));
   const int sprec = score_prec(c->cfg);                // score GEMM on the split-operand path as well
@@ -1942,11 +1988,11 @@ int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int h
       OPP_TRY(opp_b3_split(f3, f3_split, (size_t)n * C, s));
     }
     if (c->cfg.score_two_sweep == 2)   // one sweep of the split-operand GEMM (statistics + score matrix), conf formed in place
-      return opp_dual_softmax_ss_single(f3_split, f2_split, C, n, L, wc, 1.0f / (float)C, (float)((double)c->cfg.match_temperature + 1e-4),
+      return opp_dual_softmax_ss_single(f3_split, f2_split, C, n, L, wc, feat_mul, (float)((double)c->cfg.match_temperature + 1e-4),
                                         c->query_mask, c->cfg.match_thr, c->cfg.match_border_rm, kpts, base_scale, qscale, conf, stats, scratch,
                                         i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, s);
     // the score tiles are computed twice and conf is written once
-    return opp_dual_softmax_two_sweep(f3_split, f2_split, C, n, L, wc, 1.0f / (float)C, (float)((double)c->cfg.match_temperature + 1e-4),
+    return opp_dual_softmax_two_sweep(f3_split, f2_split, C, n, L, wc, feat_mul, (float)((double)c->cfg.match_temperature + 1e-4),
                                       c->query_mask, c->cfg.match_thr, c->cfg.match_border_rm, kpts, base_scale, qscale, conf, stats, scratch,
                                       i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, s);
   }
@@ -1966,7 +2012,7 @@ int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int h
   g.C = conf;
   g.ldc = L;
   g.n_store = L;
-  g.out_mul = 1.0f / (float)C;
+  g.out_mul = feat_mul;
   g.out_div = (float)((double)c->cfg.match_temperature + 1e-4);
   g.col_mask = c->query_mask;      // masked image cells get -1e9 (coarse_matching.py:108-114), or null
   // tile rows of the score GEMM: 128 (config 0 / 25); bf16x3 with enough rows: the 256x128 8-wave tile (config 20)

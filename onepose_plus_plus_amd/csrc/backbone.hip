@@ -172,6 +172,12 @@ __global__ void add4_kernel(const float4* __restrict__ a, const float4* __restri
   }
 }
 
+// out[i] = (src ? src[i] : fill) * (scale1 ? scale1[0] : 1)   (a packed norm affine: constant and / or times the layer's res_weight)
+__global__ void pack_affine_kernel(const float* __restrict__ src, float fill, const float* __restrict__ scale1, float* __restrict__ out, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (src ? src[i] : fill) * (scale1 ? scale1[0] : 1.0f);
+}
+
 // out[0 : n4a] = a + b ; out[n4a : n4a + n4c] = c   (token assembly: image tokens + sine encoding, then the cached point tokens)
 __global__ void add4_cat_kernel(const float4* __restrict__ a, const float4* __restrict__ b, size_t n4a, const float4* __restrict__ c,
                                 size_t n4c, float4* __restrict__ out) {
@@ -266,6 +272,13 @@ int opp_add(const float* a, const float* b, float* out, size_t n, hipStream_t st
   const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
   hipLaunchKernelGGL(add4_kernel, dim3(blocks), dim3(256), 0, stream, (const float4*)a, (const float4*)b, (float4*)out, n4);
   OPP_CHECK_LAUNCH("add4_kernel");
+  return OPP_OK;
+}
+
+int opp_pack_affine(const float* src, float fill, const float* scale1, float* out, int n, hipStream_t stream) {
+  OPP_CHECK_ARG(out && n > 0, "pack_affine: bad argument");
+  hipLaunchKernelGGL(pack_affine_kernel, dim3(opp_cdiv(n, 256)), dim3(256), 0, stream, src, fill, scale1, out, n);
+  OPP_CHECK_LAUNCH("pack_affine_kernel");
   return OPP_OK;
 }
 

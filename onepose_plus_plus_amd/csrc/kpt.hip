@@ -93,9 +93,13 @@ __device__ __forceinline__ void mlp_layer(const float* __restrict__ in, int in_s
   for (int i = 0; i < PPT; ++i) out[(pg + i * G) * out_stride + c] = acc[i];
 }
 
-// per-point channel norm (InstanceNorm1d applied to [B,L,C]: quirk q3) + ReLU, in place
-template <int C>
-__device__ __forceinline__ void point_norm_relu(float* __restrict__ buf, int stride, float eps) {
+// per-point channel norm (InstanceNorm1d applied to [B,L,C]: quirk q3) + ReLU, in place.  gamma / beta [C]: the affine of
+// keypoints_encoding.norm_method "layernorm" (position_encoding.py:71-72), applied behind the normalisation.  AFFINE is a template
+// parameter, not a null test: the instantiation without affine is the code as it was before the affine existed, so the compiler's
+// contraction choices -- and with them every bit of the default configuration's tokens -- stay what they were
+template <int C, bool AFFINE>
+__device__ __forceinline__ void point_norm_relu(float* __restrict__ buf, int stride, float eps, const float* __restrict__ gamma,
+                                                const float* __restrict__ beta) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int p = wave * (kPts / 4); p < (wave + 1) * (kPts / 4); ++p) {
     float* row = buf + p * stride;
@@ -110,20 +114,29 @@ __device__ __forceinline__ void point_norm_relu(float* __restrict__ buf, int str
     const float var = wave_sum_k(q) / (float)C;
     const float rstd = 1.0f / sqrtf(var + eps);
     for (int c = lane; c < C; c += 64) {
-      const float y = (row[c] - mean) * rstd;
-      row[c] = y < 0.f ? 0.f : y;   // ReLU that propagates NaN like torch (a zero-extent cloud gives NaN upstream)
+      if constexpr (AFFINE) {
+        const float y = (row[c] - mean) * rstd * gamma[c] + beta[c];
+        row[c] = y < 0.f ? 0.f : y;
+      } else {
+        const float y = (row[c] - mean) * rstd;
+        row[c] = y < 0.f ? 0.f : y;   // ReLU that propagates NaN like torch (a zero-extent cloud gives NaN upstream)
+      }
     }
   }
 }
 
 // MLP 3 -> H1 -> H2 -> H3 -> 256 with the shipped widths (32, 64, 128).
-// wt*: transposed weights [Cin][Cout]; tokens[n][c] = bank[c][n] + enc[n][c]
+// wt*: transposed weights [Cin][Cout]; tokens[n][c] = bank[c][n] + enc[n][c]; g* / be*: norm affine of the hidden layers (AFFINE only)
+template <bool AFFINE>
 __global__ __launch_bounds__(256) void kpt_encode_kernel(const float* __restrict__ kpts, const float* __restrict__ stats,
                                                          const float* __restrict__ bank, int n,
                                                          const float* __restrict__ wt0, const float* __restrict__ b0,
                                                          const float* __restrict__ wt1, const float* __restrict__ b1,
                                                          const float* __restrict__ wt2, const float* __restrict__ b2,
                                                          const float* __restrict__ wt3, const float* __restrict__ b3,
+                                                         const float* __restrict__ g0, const float* __restrict__ be0,
+                                                         const float* __restrict__ g1, const float* __restrict__ be1,
+                                                         const float* __restrict__ g2, const float* __restrict__ be2,
                                                          float* __restrict__ tokens, int ldo, float eps) {
   __shared__ float bufA[kPts * kStrideA];
   __shared__ float bufB[kPts * kStrideB];
@@ -139,15 +152,15 @@ __global__ __launch_bounds__(256) void kpt_encode_kernel(const float* __restrict
   __syncthreads();
   mlp_layer<3, 32>(bufA, kStrideA, bufB, kStrideB, wt0, b0);
   __syncthreads();
-  point_norm_relu<32>(bufB, kStrideB, eps);
+  point_norm_relu<32, AFFINE>(bufB, kStrideB, eps, g0, be0);
   __syncthreads();
   mlp_layer<32, 64>(bufB, kStrideB, bufA, kStrideA, wt1, b1);
   __syncthreads();
-  point_norm_relu<64>(bufA, kStrideA, eps);
+  point_norm_relu<64, AFFINE>(bufA, kStrideA, eps, g1, be1);
   __syncthreads();
   mlp_layer<64, 128>(bufA, kStrideA, bufB, kStrideB, wt2, b2);
   __syncthreads();
-  point_norm_relu<128>(bufB, kStrideB, eps);
+  point_norm_relu<128, AFFINE>(bufB, kStrideB, eps, g2, be2);
   __syncthreads();
   mlp_layer<128, 256>(bufB, kStrideB, bufA, kStrideA, wt3, b3);
   __syncthreads();
@@ -192,9 +205,14 @@ int opp_kpt_stats(const float* kpts, int n, float* stats, hipStream_t stream) {
 }
 
 int opp_kpt_encode(const float* kpts, const float* stats, const float* bank, int n, const float* const* wt,
-                   const float* const* bias, float* tokens, int ldo, hipStream_t stream) {
-  hipLaunchKernelGGL(kpt_encode_kernel, dim3(opp_cdiv(n, kPts)), dim3(256), 0, stream, kpts, stats, bank, n, wt[0], bias[0],
-                     wt[1], bias[1], wt[2], bias[2], wt[3], bias[3], tokens, ldo, 1e-5f);
+                   const float* const* bias, const float* const* gamma, const float* const* beta, float* tokens, int ldo,
+                   hipStream_t stream) {
+  for (int i = 0; i < 3; ++i) OPP_CHECK_ARG((gamma[i] == nullptr) == (beta[i] == nullptr), "kpt_encode: norm affine %d needs both gamma and beta", i);
+  const bool affine = gamma[0] != nullptr;
+  for (int i = 0; i < 3; ++i) OPP_CHECK_ARG((gamma[i] != nullptr) == affine, "kpt_encode: norm affine of all three hidden layers or of none");
+  hipLaunchKernelGGL(affine ? kpt_encode_kernel<true> : kpt_encode_kernel<false>, dim3(opp_cdiv(n, kPts)), dim3(256), 0, stream, kpts, stats,
+                     bank, n, wt[0], bias[0], wt[1], bias[1], wt[2], bias[2], wt[3], bias[3], gamma[0], beta[0], gamma[1], beta[1], gamma[2],
+                     beta[2], tokens, ldo, 1e-5f);
   OPP_CHECK_LAUNCH("kpt_encode_kernel");
   return OPP_OK;
 }

@@ -201,6 +201,9 @@ int opp_h2_split(const float* in, float* out, size_t n, float* scale2, hipStream
 // bf16x3 pre-split: out holds 1.5 n floats (48 B per 8 values)
 int opp_b3_split(const float* in, float* out, size_t n, hipStream_t stream);
 int opp_add(const float* a, const float* b, float* out, size_t n, hipStream_t stream);
+// out[i] = (src ? src[i] : fill) * (scale1 ? scale1[0] : 1): a norm affine vector as it is packed (constant for "instancenorm", times the
+// layer's res_weight, a ONE-element device array, under rezero)
+int opp_pack_affine(const float* src, float fill, const float* scale1, float* out, int n, hipStream_t stream);
 int opp_add_cat(const float* a, const float* b, size_t na, const float* c, size_t nc, float* out, hipStream_t stream);
 int opp_transpose(const float* in, float* out, int batch, int R, int Cc, hipStream_t stream);
 // bn_train.hip: training-mode BatchNorm (batch statistics) over an NHWC tensor [rows][ld] with C real channels:
@@ -238,8 +241,10 @@ int opp_assignmatrix(const float* kp2d_coarse, const float* kp2d_fine, int n2d, 
                      float scale_y, float coarse_scale, short* conf_gt, float* fine_loc_gt, long long* keys, int* status, hipStream_t stream);
 // kpt.hip
 int opp_kpt_stats(const float* kpts, int n, float* stats, hipStream_t stream);
+// gamma / beta [3]: affine behind the per-point norm of the three hidden layers (keypoints_encoding.norm_method "layernorm"); null entries = none
 int opp_kpt_encode(const float* kpts, const float* stats, const float* bank, int n, const float* const* wt,
-                   const float* const* bias, float* tokens, int ldo, hipStream_t stream);
+                   const float* const* bias, const float* const* gamma, const float* const* beta, float* tokens, int ldo,
+                   hipStream_t stream);
 int opp_bank_transpose(const float* bank, int n, int C, float* tokens, int ldo, hipStream_t stream);
 // coarse_match.hip
 size_t opp_coarse_match_scratch_floats(int N, int L);

@@ -60,7 +60,9 @@ def _register(root, dotted, tensor, buffer=False):
         mod.register_parameter(parts[-1], nn.Parameter(tensor))
 
 
-def _init_tensor(shape, kind):
+def _init_tensor(shape, kind, cfg=None, key=None):
+    if kind == "res_weight":    # nn.Parameter(torch.Tensor([rezero])): transformer.py:61-62
+        return torch.tensor([float(cfg[key.split(".")[0]]["rezero"])])
     if kind == "conv":      # kaiming_normal_(fan_out, relu): backbone/resnet.py:126-128
         return torch.randn(shape) * math.sqrt(2.0 / (shape[0] * shape[2] * shape[3]))
     if kind == "xavier":    # xavier_uniform_: loftr_module/transformer.py:128-131
@@ -110,20 +112,23 @@ def _validate_config(cfg):
     if ke["enable"]:
         if ke["type"] != "mlp_linear":                 # OnePosePlusModel.py:47-50
             raise NotImplementedError
-        if ke["norm_method"] != "instancenorm":
-            raise NotImplementedError("HIP path implements keypoint-encoder norm 'instancenorm' only")
+        if ke["norm_method"] == "batchnorm":
+            # nn.BatchNorm1d(channels[i]) on [B, N, channels[i]] reads N as the channel axis: upstream's forward raises
+            # "running_mean should contain N elements" unless the number of points equals the layer width
+            raise NotImplementedError("keypoint-encoder norm 'batchnorm' is not supported: upstream's forward raises for N != layer width "
+                                      "(BatchNorm1d applied to [B, N, C])")
+        if ke["norm_method"] not in ("instancenorm", "layernorm"):    # position_encoding.py:75-76
+            raise NotImplementedError
     for name in ("loftr_coarse", "loftr_fine"):
         t = cfg[name]
         if t["type"] != "LoFTR":                       # transformer.py:183-198
             raise ValueError()
-        if t["norm_method"] != "layernorm":
-            raise NotImplementedError("HIP path implements norm_method 'layernorm' only")
+        if t["norm_method"] not in ("layernorm", "instancenorm"):     # transformer.py:49-56
+            raise NotImplementedError
         # any value other than "linear" builds FullAttention (transformer.py:32-40); build_feature_map -- and with it the
         # kernel_fn check (linear_attention.py:14-18) -- is only reached by LinearAttention
         if t["attention"] == "linear" and t["kernel_fn"] != "elu + 1":
             raise ValueError()
-        if t["rezero"] is not None:
-            raise NotImplementedError("rezero is not supported")
         for n in t["layer_names"]:
             if n not in ("self", "cross"):             # transformer.py:117-120
                 raise NotImplementedError
@@ -137,8 +142,8 @@ def _validate_config(cfg):
     cm = cfg["coarse_matching"]
     if cm["type"] != "dual-softmax":                   # coarse_matching.py:63-66
         raise NotImplementedError()
-    if cm["feat_norm_method"] != "sqrt_feat_dim":
-        raise NotImplementedError("HIP path implements feat_norm_method 'sqrt_feat_dim' only")
+    if cm["feat_norm_method"] not in ("sqrt_feat_dim", "none", None, "temparature"):
+        raise ValueError                               # build_feat_normalizer in CoarseMatching.__init__ (coarse_matching.py:46-54, 60)
     if cfg["fine_matching"]["enable"] and cfg["fine_matching"]["s2d"]["type"] != "heatmap":
         raise NotImplementedError()
 
@@ -156,7 +161,7 @@ class OnePosePlus_model(nn.Module):
         _validate_config(config)
 
         for key, shape, kind in param_spec(config):
-            _register(self, key, _init_tensor(shape, kind), buffer=kind in ("bn_mean", "bn_var", "bn_count"))
+            _register(self, key, _init_tensor(shape, kind, config, key), buffer=kind in ("bn_mean", "bn_var", "bn_count"))
         if config["positional_encoding"]["enable"]:
             pe = _sine_table(config["loftr_coarse"]["d_model"], config["positional_encoding"]["pos_emb_shape"])
             self.dense_pos_encoding = _Node()
@@ -350,6 +355,10 @@ class OnePosePlus_model(nn.Module):
             arr = getattr(c, pre + "_is_cross")
             for i, n in enumerate(names):
                 arr[i] = 1 if n == "cross" else 0
+            setattr(c, pre + "_norm", 1 if t["norm_method"] == "instancenorm" else 0)
+            setattr(c, pre + "_rezero", 0 if t["rezero"] is None else 1)
+        c.kpt_norm = 1 if ke["enable"] and ke["norm_method"] == "layernorm" else 0
+        c.feat_norm = 0 if cfg["coarse_matching"]["feat_norm_method"] == "sqrt_feat_dim" else 1
         c.fine_window = int(cfg["loftr_fine"]["window_size"])
         cm = cfg["coarse_matching"]
         c.match_thr = float(cm["thr"])
@@ -520,6 +529,9 @@ class OnePosePlus_model(nn.Module):
             raise RuntimeError("query_image must be a CUDA/ROCm tensor: the HIP path has no CPU fallback")
         if img.dim() != 4 or img.size(1) != 1 or img.size(0) < 1:
             raise NotImplementedError("HIP path supports query_image of shape [B,1,H,W] (got %s)" % (tuple(img.shape),))
+        if self.config["coarse_matching"]["feat_norm_method"] == "temparature":
+            # the normaliser reads a keyword nobody passes (coarse_matching.py:51-52, :60): upstream's forward raises here as well
+            raise KeyError("temparature")
         # (the reference returns None and reports through `data`; returning the same dict as well costs nothing and lets wrappers
         # that copy their inputs -- DistributedDataParallel rebuilds every dict it is given -- hand the results back: `out = ddp(d)`)
         self._check_full_attention("query_image_mask" in data)

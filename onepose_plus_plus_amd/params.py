@@ -6,7 +6,13 @@ reference `OnePosePlus_model.state_dict()` (195 entries for the shipped config; 
   kpt_3d_pos_encoding.* src/models/OnePosePlus/utils/position_encoding.py:49-79
   loftr_coarse/fine.*   src/models/OnePosePlus/loftr_module/transformer.py:7-63, :97-126
 kind is one of: "conv", "bn_weight", "bn_bias", "bn_mean", "bn_var", "bn_count",
-"linear_w", "linear_b", "xavier", "ln_weight", "ln_bias".
+"linear_w", "linear_b", "xavier", "ln_weight", "ln_bias", "res_weight".
+
+Keys that depend on a setting (upstream registers them the same way):
+  loftr_*.rezero = a number            <level>.layers.<i>.res_weight [1] in front of the layer's q_proj.weight (the layer's own
+                                       parameter precedes its sub-modules'), initialised to that number (transformer.py:61-63)
+  loftr_*.norm_method "instancenorm"   no norm1 / norm2 keys (nn.InstanceNorm1d: affine = False, no running statistics)
+  keypoints_encoding.norm_method "layernorm"   kpt_3d_pos_encoding.encoder.{1,4,7}.{weight,bias} (nn.LayerNorm of each hidden layer)
 """
 
 
@@ -61,11 +67,14 @@ def kpt_encoder_spec(cfg):
     k = cfg["keypoints_encoding"]
     chans = [3] + list(k["keypoints_encoder"]) + [k["descriptor_dim"]]
     s = []
-    # nn.Sequential indices: Linear, InstanceNorm1d, ReLU triples -> 0, 3, 6, 9
+    # nn.Sequential indices: Linear, norm, ReLU triples -> Linears at 0, 3, 6, 9; norm_method "layernorm" puts an affine at 1, 4, 7
     for i in range(1, len(chans)):
         idx = 3 * (i - 1)
         s.append(("kpt_3d_pos_encoding.encoder.%d.weight" % idx, (chans[i], chans[i - 1]), "linear_w"))
         s.append(("kpt_3d_pos_encoding.encoder.%d.bias" % idx, (chans[i],), "linear_b"))
+        if k["norm_method"] == "layernorm" and i < len(chans) - 1:
+            s.append(("kpt_3d_pos_encoding.encoder.%d.weight" % (idx + 1), (chans[i],), "ln_weight"))
+            s.append(("kpt_3d_pos_encoding.encoder.%d.bias" % (idx + 1), (chans[i],), "ln_bias"))
     return s
 
 
@@ -75,6 +84,8 @@ def transformer_spec(name, tcfg):
     s = []
     for i in range(n_layers):
         p = "%s.layers.%d" % (name, i)
+        if tcfg["rezero"] is not None:
+            s.append((p + ".res_weight", (1,), "res_weight"))
         s += [
             (p + ".q_proj.weight", (d, d), "xavier"),
             (p + ".k_proj.weight", (d, d), "xavier"),
@@ -82,11 +93,14 @@ def transformer_spec(name, tcfg):
             (p + ".merge.weight", (d, d), "xavier"),
             (p + ".mlp.0.weight", (2 * d, 2 * d), "xavier"),
             (p + ".mlp.2.weight", (d, 2 * d), "xavier"),
-            (p + ".norm1.weight", (d,), "ln_weight"),
-            (p + ".norm1.bias", (d,), "ln_bias"),
-            (p + ".norm2.weight", (d,), "ln_weight"),
-            (p + ".norm2.bias", (d,), "ln_bias"),
         ]
+        if tcfg["norm_method"] != "instancenorm":
+            s += [
+                (p + ".norm1.weight", (d,), "ln_weight"),
+                (p + ".norm1.bias", (d,), "ln_bias"),
+                (p + ".norm2.weight", (d,), "ln_weight"),
+                (p + ".norm2.bias", (d,), "ln_bias"),
+            ]
     if tcfg.get("final_proj"):      # constructed upstream but never applied (transformer.py:123-124):
         s += [(name + ".final_proj.weight", (d, d), "xavier"),      # kept so that a strict load of such a checkpoint works
               (name + ".final_proj.bias", (d,), "linear_b")]

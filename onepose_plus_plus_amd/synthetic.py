@@ -46,6 +46,9 @@ def make_state_dict(cfg, seed=0, randomize_norm=True):
             t = torch.rand(shape, generator=g) + 0.5 if randomize_norm else torch.ones(shape)
         elif kind == "bn_count":
             t = torch.tensor(0, dtype=torch.int64)
+        elif kind == "res_weight":
+            # away from 0 (the layer would be the identity) and from 1 (rezero would not show)
+            t = torch.rand(shape, generator=g) * 0.75 + 0.25
         else:
             raise ValueError(kind)
         sd[key] = t

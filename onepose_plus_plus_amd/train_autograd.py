@@ -172,7 +172,8 @@ class HipLayerNorm(torch.autograd.Function):
             _lib.check(lib.opp_layer_norm_train_backward(g2.data_ptr(), x2.data_ptr(), g.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, C,
                                                          dx.data_ptr(), dg.data_ptr(), db.data_ptr(), ws.data_ptr(), nb,
                                                          torch.cuda.current_stream(dev).cuda_stream), "opp_layer_norm_train_backward")
-        return dx.view(*ctx.lead, C), dg, db
+        # (constant ones / zeros of norm_method "instancenorm" take no gradient)
+        return dx.view(*ctx.lead, C), dg if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
 
 
 def _linear(x, w, hp=None):
@@ -194,7 +195,8 @@ def _kpt_encoding(p, kpts, desc, hp=None):
     extent = kpts[0].max(dim=0).values - kpts[0].min(dim=0).values
     x = (kpts - kpts.mean(dim=-2, keepdim=True)) / (extent.max() * 0.6)
     pre = "kpt_3d_pos_encoding.encoder."
-    idxs = sorted({int(k[len(pre):].split(".")[0]) for k in p if k.startswith(pre)})
+    # nn.Sequential of (Linear, norm, ReLU) triples: the Linears sit at 0, 3, 6, ...; keys at 1, 4, 7 are the affine of norm_method "layernorm"
+    idxs = sorted({int(k[len(pre):].split(".")[0]) for k in p if k.startswith(pre)} - {1, 4, 7})
     for n, i in enumerate(idxs):
         w, bias = p[pre + "%d.weight" % i], p[pre + "%d.bias" % i]
         if hp is not None and x.is_cuda and w.shape[0] % 32 == 0:
@@ -206,7 +208,10 @@ def _kpt_encoding(p, kpts, desc, hp=None):
         if n < len(idxs) - 1:
             mu = x.mean(dim=-1, keepdim=True)
             var = x.var(dim=-1, unbiased=False, keepdim=True)
-            x = F.relu((x - mu) / torch.sqrt(var + _EPS_LN))
+            x = (x - mu) / torch.sqrt(var + _EPS_LN)
+            if pre + "%d.weight" % (i + 1) in p:                     # nn.LayerNorm(channels[i]): position_encoding.py:71-72
+                x = x * p[pre + "%d.weight" % (i + 1)] + p[pre + "%d.bias" % (i + 1)]
+            x = F.relu(x)
     return desc + x.transpose(2, 1)
 
 
@@ -224,6 +229,15 @@ def _linear_attention(q, k, v, q_mask=None, kv_mask=None, eps=1e-6, hp=None):   
     KV = torch.einsum("nshd,nshv->nhdv", K, v)
     Z = 1 / (torch.einsum("nlhd,nhd->nlh", Q, K.sum(dim=1)) + eps)
     return torch.einsum("nlhd,nhdv,nlh->nlhv", Q, KV, Z) * S
+
+
+def _norm_affine(p, name, ref):
+    """(weight, bias) of a layer norm; norm_method "instancenorm" has no such keys (nn.InstanceNorm1d(d_model) on [N, L, C] tokens = the
+    same per-token normalisation without affine): constant ones / zeros, which need no gradient"""
+    if name + ".weight" in p:
+        return p[name + ".weight"], p[name + ".bias"]
+    C = ref.shape[-1]
+    return ref.new_ones(C), ref.new_zeros(C)
 
 
 def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=None):      # loftr_module/transformer.py:65-94
@@ -244,9 +258,12 @@ def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=
         k = _linear(source, wk).view(B, -1, nhead, D)
         v = _linear(source, wv).view(B, -1, nhead, D)
     msg = _linear_attention(q, k, v, x_mask, source_mask, hp=hp).reshape(B, -1, C)
-    msg = _layer_norm(_linear(msg, p[name + ".merge.weight"], hp), p[name + ".norm1.weight"], p[name + ".norm1.bias"], hp)
+    msg = _layer_norm(_linear(msg, p[name + ".merge.weight"], hp), *_norm_affine(p, name + ".norm1", x), hp)
     msg = _linear(F.relu(_linear(torch.cat([x, msg], dim=2), p[name + ".mlp.0.weight"], hp)), p[name + ".mlp.2.weight"], hp)
-    return x + _layer_norm(msg, p[name + ".norm2.weight"], p[name + ".norm2.bias"], hp)
+    msg = _layer_norm(msg, *_norm_affine(p, name + ".norm2", x), hp)
+    if name + ".res_weight" in p:                                    # rezero (transformer.py:94)
+        msg = p[name + ".res_weight"] * msg
+    return x + msg
 
 
 def _transformer(p, name, tcfg, f3, f2, mask=None, hp=None):      # loftr_module/transformer.py:133-171 (f3 already [B, N, C])
@@ -409,6 +426,8 @@ class HipCoarseMatch(torch.autograd.Function):
         aux.update({"i_all": i_all, "j_all": j_all, "c_all": c_all, "counts": counts})
         ctx.save_for_backward(f3c, f2c)
         ctx.mask, ctx.hp = mask, aux["hp"]
+        if model.config["coarse_matching"]["feat_norm_method"] != "sqrt_feat_dim":      # "none" / None: coarse_matching.py:49-50
+            C = 1
         ctx.scale = (1.0 / C) / (float(model.config["coarse_matching"]["dual_softmax"]["temperature"]) + 1e-4)
         return conf
 
