@@ -646,7 +646,7 @@ extern "C" int opp_pack_train_weights(opp_ctx* c, const float* const* w, int n, 
 // ----------------------------------------------------------------------------------------
 namespace {
 
-// split-K scratch of the convolutions this host thread is enqueuing (backbone_impl sets it per stream branch; null = never split)
+// split-K scratch of the convolutions this host thread is enqueuing (the backbone stages set it per stream branch; null = never split)
 constexpr size_t kSplitKScratchFloats = (size_t)4 << 20;      // 4 slices of <= 64 tiles of 128 x 128
 thread_local float* t_splitk_ws = nullptr;
 thread_local size_t t_splitk_ws_floats = 0;
@@ -876,91 +876,103 @@ OppGemm stem_gemm(const opp_ctx* c, const float* col, int M, const float* w, con
   return g;
 }
 
-// phase 0: the whole ResNetFPN_8_2.forward; 1: stem .. layer3 + layer3_outconv (-> feat_c, the coarse map);
-// 2: the FPN fine branch (-> feat_f), which needs only x1, x2 and feat_c of phase 1 -- the coarse level does not depend on it;
-// 3: the 1/4-resolution half of that branch only (-> x2_out); 4: its 1/2-resolution half (x1, x2_out -> feat_f; bufs prepared by the caller).
-// x1_ext / x2o_ext: caller-owned buffers that receive x1 / x2_out instead of the workspace (match-driven fine branch).
-int backbone_impl(opp_ctx* c, const float* image, int H, int W, float* feat_c, float* feat_f, Arena& a, hipStream_t s, int phase = 0,
-                  BackboneBufs* bufs = nullptr, float* x1_ext = nullptr, float* x2o_ext = nullptr) {
-  AspScope asp_scope;
+// pre-split twin of a map: kept when one of its consumers takes it (conv_takes_split); the fp32 copy: dropped when all of them do
+void* twin(void* buf, int hp, std::initializer_list<const ConvDesc*> consumers) {
+  for (const ConvDesc* d : consumers)
+    if (buf && conv_takes_split(*d, hp)) return buf;
+  return nullptr;
+}
+float* fp32_of(float* buf, void* tw, int hp, std::initializer_list<const ConvDesc*> consumers) {
+  if (!tw) return buf;
+  for (const ConvDesc* d : consumers)
+    if (!conv_takes_split(*d, hp)) return buf;
+  return nullptr;
+}
+
+// The eval-mode ResNetFPN_8_2.forward as three stages over one planned BackboneBufs: the trunk (stem .. layer3_outconv -> feat_c; the coarse
+// level needs nothing else), the FPN fine branch at 1/4 (x2, feat_c -> x2_out) and at 1/2 resolution (x1, x2_out -> feat_f).  An entry call takes
+// one AspScope around them and prepares once, before any launch; the trunk's twin decisions (b.x1s, b.x2s) reach the fine stages through b.
+int backbone_checks(const opp_ctx* c, int H, int W) {
   OPP_CHECK_ARG(c && c->packed, "backbone: weights not packed");
   OPP_CHECK_ARG(c->bn_packed, "backbone: weights were packed with scope 1 (training step: no BatchNorm-folded convolutions); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone: H,W must be multiples of 8 (got %dx%d)", H, W);
-  BackboneBufs local;
-  BackboneBufs& b = bufs ? *bufs : local;
-  if (phase == 0 || phase == 1) {
-    plan_backbone(c, 1, H, W, true, a, b);
-    if (!a.ok) {
-      opp_set_error("backbone: workspace too small");
-      return OPP_ERR_WORKSPACE;
-    }
-    if (x1_ext) b.x1 = x1_ext;
-    if (x2o_ext) b.x2o = x2o_ext;
-  }
-  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
-  const int hp = gemm_prec(c->cfg);
-  // pre-split twin of a map: kept when one of its consumers takes it (conv_takes_split); the fp32 copy: dropped when all of them do
-  auto twin = [&](void* buf, std::initializer_list<const ConvDesc*> consumers) -> void* {
-    if (buf)
-      for (const ConvDesc* d : consumers)
-        if (conv_takes_split(*d, hp)) return buf;
-    return nullptr;
-  };
-  auto fp32_of = [&](float* buf, void* tw, std::initializer_list<const ConvDesc*> consumers) -> float* {
-    if (!tw) return buf;
-    for (const ConvDesc* d : consumers)
-      if (!conv_takes_split(*d, hp)) return buf;
-    return nullptr;
-  };
-  const BlockDesc* B = c->blocks;
-  if (phase == 0 || phase == 1) {
-    SplitKScope sk_scope(b.sk1);
-    // stem: conv7x7/s2 + BN + ReLU (resnet.py:143): one direct kernel (bf16x3), else im2col + GEMM -- bit-identical
-    const char* stem_env = getenv("OPP_STEM_DIRECT");          // A/B switch of the tests / tools
-    void* x0s = nullptr;
-    if (opp_stem_direct_ok(c->stem.cout, hp) && pad32(c->stem.cout) == c->stem.cout && !(stem_env && stem_env[0] == '0') &&
-        (size_t)H2 * W2 * pad32(c->stem.cout) < (1ull << 31)) {
-      x0s = twin(b.x0s, {&B[0].conv1});
-      OPP_TRY(opp_stem_direct(image, H, W, c->stem.w, c->stem.bias, b.x0, pad32(c->stem.cout), s, x0s, (int)split_row_bytes(pad32(c->stem.cout))));
-    } else {
-      OPP_TRY(opp_stem_im2col(image, 1, H, W, b.col, s));
-      OPP_TRY(opp_gemm_launch(stem_gemm(c, b.col, H2 * W2, c->stem.w, c->stem.h2s, c->stem.bias, OPP_ACT_RELU, b.x0), s));
-    }
-    // (x0, x1a, x3a are shortcuts and x1 / x2 may leave through x1_ext / feed a convolution with a packed K tail: those keep their fp32 copy)
-    void* x1as = twin(b.x1as, {&B[1].conv1});
-    OPP_TRY(run_block(b.x0, H2, W2, B[0], 1, b.t1, nullptr, b.x1a, s, hp, {.x3 = x0s, .tmp3 = b.t1s, .y3 = x1as}));   // layer1 (:144)
-    b.x1s = twin(b.x1s, {&B[2].conv1, &B[2].down, &c->l1_out});
-    OPP_TRY(run_block(b.x1a, H2, W2, B[1], 1, b.t1, nullptr, b.x1, s, hp, {.x3 = x1as, .tmp3 = b.t1s, .y3 = b.x1s}));
-    OPP_TRY(run_block(b.x1, H2, W2, B[2], 2, b.t2, b.ds2, b.x2a, s, hp, {.x3 = b.x1s}));                              // layer2 (:145)
-    b.x2s = twin(b.x2s, {&B[4].conv1, &B[4].down, &c->l2_out});
-    OPP_TRY(run_block(b.x2a, H4, W4, B[3], 1, b.t2, nullptr, b.x2, s, hp, {.y3 = b.x2s}));
-    void* x3as = twin(b.x3as, {&B[5].conv1});
-    OPP_TRY(run_block(b.x2, H4, W4, B[4], 2, b.t3, b.ds3, b.x3a, s, hp, {.x3 = b.x2s, .tmp3 = b.t3s, .y3 = x3as}));   // layer3 (:146)
-    void* x3s = twin(b.x3s, {&c->l3_out});
-    float* x3f = fp32_of(b.x3, x3s, {&c->l3_out});
-    OPP_TRY(run_block(b.x3a, H8, W8, B[5], 1, b.t3, nullptr, x3f, s, hp, {.x3 = x3as, .tmp3 = b.t3s, .y3 = x3s}));
-    // FPN (:149-157)
-    OPP_TRY(run_conv(x3f, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, {.x3 = x3s}));
-  }
-  if (phase == 0 || phase == 2 || phase == 3) {
-    SplitKScope sk_scope(b.sk2);
-    void* l2s = twin(b.l2s, {&c->l2_out2a});
-    float* l2f = fp32_of(b.l2, l2s, {&c->l2_out2a});
-    OPP_TRY(run_conv(b.x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, l2f, s, hp, {.x3 = b.x2s, .y3 = l2s}));
-    void* u2s = twin(b.u2s, {&c->l2_out2b});
-    float* u2f = fp32_of(b.u2, u2s, {&c->l2_out2b});
-    OPP_TRY(run_conv(l2f, H4, W4, c->l2_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, u2f, s, hp, {.x3 = l2s, .y3 = u2s}));
-    OPP_TRY(run_conv(u2f, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.x2o, s, hp, {.x3 = u2s}));
-  }
-  if (phase == 0 || phase == 2 || phase == 4) {
-    SplitKScope sk_scope(b.sk2);
-    static const int l1out_cfg = getenv("OPP_L1OUT_CFG") ? atoi(getenv("OPP_L1OUT_CFG")) : -1;   // A/B switch (tools): tile of the K = 128 lateral
-    OPP_TRY(run_conv(b.x1, H2, W2, c->l1_out, 1, b.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l1, s, hp,
-                     {.tile_cfg = hp == OPP_PREC_BF16X3 ? l1out_cfg : -1, .x3 = b.x1s}));
-    OPP_TRY(run_conv(b.l1, H2, W2, c->l1_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, b.u1, s, hp));
-    OPP_TRY(run_conv(b.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp));
-  }
   return OPP_OK;
+}
+int backbone_prepare(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b, float* x1_ext = nullptr, float* x2o_ext = nullptr) {
+  OPP_TRY(backbone_checks(c, H, W));
+  plan_backbone(c, 1, H, W, true, a, b);
+  if (!a.ok) {
+    opp_set_error("backbone: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
+  if (x1_ext) b.x1 = x1_ext;       // caller-owned buffers receive x1 / x2_out instead of the workspace (match-driven fine branch)
+  if (x2o_ext) b.x2o = x2o_ext;
+  return OPP_OK;
+}
+int backbone_trunk(const opp_ctx* c, const float* image, int H, int W, float* feat_c, BackboneBufs& b, hipStream_t s) {
+  const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8, hp = gemm_prec(c->cfg);
+  const BlockDesc* B = c->blocks;
+  SplitKScope sk_scope(b.sk1);
+  // stem: conv7x7/s2 + BN + ReLU (resnet.py:143): one direct kernel (bf16x3), else im2col + GEMM -- bit-identical
+  const char* stem_env = getenv("OPP_STEM_DIRECT");          // A/B switch of the tests / tools
+  void* x0s = nullptr;
+  if (opp_stem_direct_ok(c->stem.cout, hp) && pad32(c->stem.cout) == c->stem.cout && !(stem_env && stem_env[0] == '0') &&
+      (size_t)H2 * W2 * pad32(c->stem.cout) < (1ull << 31)) {
+    x0s = twin(b.x0s, hp, {&B[0].conv1});
+    OPP_TRY(opp_stem_direct(image, H, W, c->stem.w, c->stem.bias, b.x0, pad32(c->stem.cout), s, x0s, (int)split_row_bytes(pad32(c->stem.cout))));
+  } else {
+    OPP_TRY(opp_stem_im2col(image, 1, H, W, b.col, s));
+    OPP_TRY(opp_gemm_launch(stem_gemm(c, b.col, H2 * W2, c->stem.w, c->stem.h2s, c->stem.bias, OPP_ACT_RELU, b.x0), s));
+  }
+  // (x0, x1a, x3a are shortcuts and x1 / x2 may leave through x1_ext / feed a convolution with a packed K tail: those keep their fp32 copy)
+  void* x1as = twin(b.x1as, hp, {&B[1].conv1});
+  OPP_TRY(run_block(b.x0, H2, W2, B[0], 1, b.t1, nullptr, b.x1a, s, hp, {.x3 = x0s, .tmp3 = b.t1s, .y3 = x1as}));   // layer1 (:144)
+  b.x1s = twin(b.x1s, hp, {&B[2].conv1, &B[2].down, &c->l1_out});
+  OPP_TRY(run_block(b.x1a, H2, W2, B[1], 1, b.t1, nullptr, b.x1, s, hp, {.x3 = x1as, .tmp3 = b.t1s, .y3 = b.x1s}));
+  OPP_TRY(run_block(b.x1, H2, W2, B[2], 2, b.t2, b.ds2, b.x2a, s, hp, {.x3 = b.x1s}));                              // layer2 (:145)
+  b.x2s = twin(b.x2s, hp, {&B[4].conv1, &B[4].down, &c->l2_out});
+  OPP_TRY(run_block(b.x2a, H4, W4, B[3], 1, b.t2, nullptr, b.x2, s, hp, {.y3 = b.x2s}));
+  void* x3as = twin(b.x3as, hp, {&B[5].conv1});
+  OPP_TRY(run_block(b.x2, H4, W4, B[4], 2, b.t3, b.ds3, b.x3a, s, hp, {.x3 = b.x2s, .tmp3 = b.t3s, .y3 = x3as}));   // layer3 (:146)
+  void* x3s = twin(b.x3s, hp, {&c->l3_out});
+  float* x3f = fp32_of(b.x3, x3s, hp, {&c->l3_out});
+  OPP_TRY(run_block(b.x3a, H8, W8, B[5], 1, b.t3, nullptr, x3f, s, hp, {.x3 = x3as, .tmp3 = b.t3s, .y3 = x3s}));
+  return run_conv(x3f, H8, W8, c->l3_out, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_c, s, hp, {.x3 = x3s});   // FPN (:149-157)
+}
+int backbone_fine_quarter(const opp_ctx* c, int H, int W, const float* feat_c, const BackboneBufs& b, hipStream_t s) {
+  const int H4 = H / 4, W4 = W / 4, hp = gemm_prec(c->cfg);
+  SplitKScope sk_scope(b.sk2);
+  void* l2s = twin(b.l2s, hp, {&c->l2_out2a});
+  float* l2f = fp32_of(b.l2, l2s, hp, {&c->l2_out2a});
+  OPP_TRY(run_conv(b.x2, H4, W4, c->l2_out, 1, feat_c, OPP_RES_BILINEAR2X, OPP_ACT_NONE, l2f, s, hp, {.x3 = b.x2s, .y3 = l2s}));
+  void* u2s = twin(b.u2s, hp, {&c->l2_out2b});
+  float* u2f = fp32_of(b.u2, u2s, hp, {&c->l2_out2b});
+  OPP_TRY(run_conv(l2f, H4, W4, c->l2_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, u2f, s, hp, {.x3 = l2s, .y3 = u2s}));
+  return run_conv(u2f, H4, W4, c->l2_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.x2o, s, hp, {.x3 = u2s});
+}
+int backbone_fine_half(const opp_ctx* c, int H, int W, float* feat_f, const BackboneBufs& b, hipStream_t s) {
+  const int H2 = H / 2, W2 = W / 2, hp = gemm_prec(c->cfg);
+  SplitKScope sk_scope(b.sk2);
+  static const int l1out_cfg = getenv("OPP_L1OUT_CFG") ? atoi(getenv("OPP_L1OUT_CFG")) : -1;   // A/B switch (tools): tile of the K = 128 lateral
+  OPP_TRY(run_conv(b.x1, H2, W2, c->l1_out, 1, b.x2o, OPP_RES_BILINEAR2X, OPP_ACT_NONE, b.l1, s, hp,
+                   {.tile_cfg = hp == OPP_PREC_BF16X3 ? l1out_cfg : -1, .x3 = b.x1s}));
+  OPP_TRY(run_conv(b.l1, H2, W2, c->l1_out2a, 1, nullptr, OPP_RES_NONE, OPP_ACT_LEAKY, b.u1, s, hp));
+  return run_conv(b.u1, H2, W2, c->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, feat_f, s, hp);
+}
+// what of the fine branch a caller wants, in order, on one stream: nothing (no fine stage follows, nothing reads the fine map: ~44 % of the
+// backbone FLOPs not launched), the 1/4-resolution stage only (match-driven fine branch: x1 / x2_out are kept), or the whole (-> feat_f)
+enum class FineWant { None, Quarter, Whole };
+int backbone_fine(const opp_ctx* c, int H, int W, const float* feat_c, float* feat_f, const BackboneBufs& b, FineWant want, hipStream_t s) {
+  if (want != FineWant::None) OPP_TRY(backbone_fine_quarter(c, H, W, feat_c, b, s));
+  return want == FineWant::Whole ? backbone_fine_half(c, H, W, feat_f, b, s) : OPP_OK;
+}
+// opp_backbone_fine_branch: the 1/2-resolution stage alone, from the caller's x1 / x2_out (every other map and every twin of b stays null)
+size_t plan_fine_branch(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b) {
+  const size_t p2 = (size_t)(H / 2) * (W / 2);
+  b.l1 = a.f(p2 * pad32(c->cfg.block_dims[1]));
+  b.u1 = a.f(p2 * pad32(c->cfg.block_dims[1]));
+  b.sk2 = a.f(kSplitKScratchFloats);      // small images: these convolutions run as K slices, as inside the one-call path
+  return a.off;
 }
 
 }  // namespace
@@ -1429,7 +1441,11 @@ extern "C" int opp_backbone(opp_ctx* ctx, const float* image, int H, int W, floa
   FlagScope flag_scope(ctx);
   OPP_CHECK_ARG(ctx && image && feat_c && feat_f && ws, "backbone: null argument");
   Arena a(ws, ws_bytes);
-  return backbone_impl(ctx, image, H, W, feat_c, feat_f, a, (hipStream_t)stream);
+  AspScope asp_scope;
+  BackboneBufs b;
+  OPP_TRY(backbone_prepare(ctx, H, W, a, b));
+  OPP_TRY(backbone_trunk(ctx, image, H, W, feat_c, b, (hipStream_t)stream));
+  return backbone_fine(ctx, H, W, feat_c, feat_f, b, FineWant::Whole, (hipStream_t)stream);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2071,6 +2087,41 @@ size_t plan_forward_coarse(const opp_ctx* c, int H, int W, int n, Arena& a, floa
   return a.off;
 }
 
+// The FPN fine branch (six chip-filling convolutions that only the fine stage needs) beside the coarse level (many short launches that leave
+// CUs idle and depend on the coarse map alone): a side stream forked from the caller's stream s after the trunk, joined before the call returns
+struct SideBranch {
+  opp_ctx* c;
+  hipStream_t s;
+  bool joining = false;   // ev_join is recorded: s has to wait for it
+  // the stream and its two events, created on first use -- all three or none: a half-built set must never be seen by a later call
+  int ensure() {
+    if (c->side_stream) return OPP_OK;
+    hipStream_t st = nullptr;
+    hipEvent_t ef = nullptr, ej = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&ef, hipEventDisableTiming) == hipSuccess &&
+        hipEventCreateWithFlags(&ej, hipEventDisableTiming) == hipSuccess) {
+      c->side_stream = st;
+      c->ev_fork = ef;
+      c->ev_join = ej;
+      return OPP_OK;
+    }
+    if (ej) (void)hipEventDestroy(ej);
+    if (ef) (void)hipEventDestroy(ef);
+    if (st) (void)hipStreamDestroy(st);
+    opp_set_error("forward_coarse: cannot create the side stream of the fine-branch overlap");
+    return OPP_ERR_LAUNCH;
+  }
+  // false: the dependency cannot be expressed, and the caller runs the branch on s (same kernels, no overlap)
+  bool fork() { return hipEventRecord(c->ev_fork, s) == hipSuccess && hipStreamWaitEvent(c->side_stream, c->ev_fork, 0) == hipSuccess; }
+  // after the side stream's last launch; a join that cannot be expressed as an event: the host waits here, before anything reuses the buffers
+  void join() {
+    joining = hipEventRecord(c->ev_join, c->side_stream) == hipSuccess;
+    if (!joining) (void)hipStreamSynchronize(c->side_stream);
+  }
+  // every exit path re-joins (never unsynchronised): feat_f and the workspace are the caller's again in stream order
+  ~SideBranch() { if (joining && hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(c->side_stream); }
+};
+
 }  // namespace
 
 extern "C" size_t opp_forward_coarse_workspace_bytes(const opp_ctx* ctx, int H, int W, int n) {
@@ -2111,74 +2162,22 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   size_t mark = a.off;
   const EncLevel lv = level_of(ctx, 0);
   const int hc = H / 8, wc = W / 8, L = hc * wc, C = lv.C;
-  bool forked = false;
-  // what runs beside the coarse level: the whole FPN fine branch (-> feat_f), or -- match-driven fine branch, opp_set_fine_patch_buffers --
-  // only its 1/4-resolution half (-> x2_out; x1 / x2_out land in the caller's buffers), or nothing (feat_f = NULL: the fine map is dead)
-  const bool keep_inputs = !feat_f && ctx->fine_x1 && ctx->fine_x2o;
-  const int side_phase = feat_f ? 2 : (keep_inputs ? 3 : 0);
-  if (side_phase == 0) {
-    // the caller runs no fine stage (fine_matching.enable = False): the fine map is not an output of the forward and nothing
-    // downstream reads it, so the FPN fine branch (x1_out; ~44 % of the backbone FLOPs) is not launched
-    BackboneBufs bufs;
-    OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, nullptr, a, s, 1, &bufs));
-  } else if (ctx->cfg.fpn_overlap) {
-    // The coarse level (tokens, transformer, matcher: many short launches that leave CUs idle) depends only on the
-    // coarse map; the FPN fine branch (six chip-filling convolutions, ~40 % of the backbone FLOPs) is needed by the fine
-    // stage only.  Run the fine branch on a side stream next to the coarse level: fork after layer3_outconv, join below.
-    if (!ctx->side_stream) {
-      // all three objects or none: a half-built set must never be seen by a later call
-      hipStream_t st = nullptr;
-      hipEvent_t ef = nullptr, ej = nullptr;
-      const bool ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
-                      hipEventCreateWithFlags(&ef, hipEventDisableTiming) == hipSuccess &&
-                      hipEventCreateWithFlags(&ej, hipEventDisableTiming) == hipSuccess;
-      if (!ok) {
-        if (ej) (void)hipEventDestroy(ej);
-        if (ef) (void)hipEventDestroy(ef);
-        if (st) (void)hipStreamDestroy(st);
-        opp_set_error("forward_coarse: cannot create the side stream of the fine-branch overlap");
-        return OPP_ERR_LAUNCH;
-      }
-      ctx->side_stream = st;
-      ctx->ev_fork = ef;
-      ctx->ev_join = ej;
-    }
-    BackboneBufs bufs;
-    OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, feat_f, a, s, 1, &bufs, keep_inputs ? ctx->fine_x1 : nullptr, keep_inputs ? ctx->fine_x2o : nullptr));
-    mark = a.off;                                    // the backbone buffers stay alive until the join
-    // fork: if the dependency cannot be expressed the fine branch runs on the caller's stream (same kernels, no overlap)
-    const bool fork_ok = hipEventRecord(ctx->ev_fork, s) == hipSuccess && hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0) == hipSuccess;
-    if (!fork_ok) {
-      OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, feat_f, a, s, side_phase, &bufs));
-    } else {
-      const int rc = backbone_impl(ctx, image, H, W, feat_c, feat_f, a, ctx->side_stream, side_phase, &bufs);
-      if (hipEventRecord(ctx->ev_join, ctx->side_stream) != hipSuccess) {
-        // the join cannot be expressed as an event: wait for the side stream on the host before anything reuses its buffers
-        (void)hipStreamSynchronize(ctx->side_stream);
-        if (rc != OPP_OK) return rc;
-      } else {
-        forked = true;
-        if (rc != OPP_OK) {
-          if (hipStreamWaitEvent(s, ctx->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(ctx->side_stream);
-          return rc;
-        }
-      }
-    }
-  } else if (keep_inputs) {
-    BackboneBufs bufs;
-    OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, nullptr, a, s, 1, &bufs, ctx->fine_x1, ctx->fine_x2o));
-    OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, nullptr, a, s, 3, &bufs));
-  } else {
-    OPP_TRY(backbone_impl(ctx, image, H, W, feat_c, feat_f, a, s));
+  const bool keep_inputs = !feat_f && ctx->fine_x1 && ctx->fine_x2o;   // opp_set_fine_patch_buffers: x1 / x2_out land in the caller's buffers
+  const FineWant want = feat_f ? FineWant::Whole : (keep_inputs ? FineWant::Quarter : FineWant::None);
+  const bool overlap = want != FineWant::None && ctx->cfg.fpn_overlap;
+  SideBranch side{ctx, s};
+  if (overlap) OPP_TRY(side.ensure());
+  {
+    AspScope asp_scope;
+    BackboneBufs b;
+    OPP_TRY(backbone_prepare(ctx, H, W, a, b, keep_inputs ? ctx->fine_x1 : nullptr, keep_inputs ? ctx->fine_x2o : nullptr));
+    OPP_TRY(backbone_trunk(ctx, image, H, W, feat_c, b, s));
+    if (overlap) mark = a.off;                       // the backbone buffers stay alive until the join
+    const bool forked = overlap && side.fork();
+    const int rc = backbone_fine(ctx, H, W, feat_c, feat_f, b, want, forked ? ctx->side_stream : s);
+    if (forked) side.join();
+    OPP_TRY(rc);
   }
-  struct Join {       // every exit path re-joins the side stream: feat_f and the workspace are the caller's again in stream order
-    opp_ctx* c;
-    hipStream_t s;
-    bool on;
-    ~Join() {
-      if (on && hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(c->side_stream);   // never unsynchronised
-    }
-  } join{ctx, s, forked};
   a.off = mark;
   // resident object with a transformer prefix (opp_set_object_prefix): its 3D tokens enter already past layer 0
   const bool use_prefix = ctx->obj_prefix != nullptr && ctx->obj_prefix_n == n && tokens3d_pre != nullptr && obj_prefix_ok(ctx);
@@ -2298,7 +2297,9 @@ extern "C" int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_o
 
 extern "C" size_t opp_backbone_fine_branch_workspace_bytes(const opp_ctx* ctx, int H, int W) {
   if (!ctx) return 0;
-  return 2 * opp_align((size_t)(H / 2) * (W / 2) * pad32(ctx->cfg.block_dims[1]) * sizeof(float)) + opp_align(kSplitKScratchFloats * sizeof(float)) + 1024;
+  Arena a(nullptr, 0);
+  BackboneBufs b{};
+  return opp_align(plan_fine_branch(ctx, H, W, a, b)) + 1024;
 }
 
 // The dense 1/2-resolution half of the FPN fine branch from kept x1 / x2_out (more matches than the patch pyramid pays for): -> feat_f
@@ -2309,17 +2310,16 @@ extern "C" int opp_backbone_fine_branch(opp_ctx* ctx, const float* x1, const flo
   OPP_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_fine_branch: H,W must be multiples of 8 (got %dx%d)", H, W);
   Arena a(ws, ws_bytes);
   BackboneBufs b{};
-  const size_t p2 = (size_t)(H / 2) * (W / 2);
-  b.x1 = const_cast<float*>(x1);
-  b.x2o = const_cast<float*>(x2_out);
-  b.l1 = a.f(p2 * pad32(ctx->cfg.block_dims[1]));
-  b.u1 = a.f(p2 * pad32(ctx->cfg.block_dims[1]));
-  b.sk2 = a.f(kSplitKScratchFloats);      // small images: these convolutions run as K slices, as inside the one-call path
+  plan_fine_branch(ctx, H, W, a, b);
   if (!a.ok) {
     opp_set_error("backbone_fine_branch: workspace too small");
     return OPP_ERR_WORKSPACE;
   }
-  return backbone_impl(ctx, nullptr, H, W, nullptr, feat_f, a, (hipStream_t)stream, 4, &b);
+  b.x1 = const_cast<float*>(x1);
+  b.x2o = const_cast<float*>(x2_out);
+  AspScope asp_scope;
+  OPP_TRY(backbone_checks(ctx, H, W));
+  return backbone_fine_half(ctx, H, W, feat_f, b, (hipStream_t)stream);
 }
 
 extern "C" size_t opp_fine_workspace_bytes(const opp_ctx* ctx, int M) {

@@ -295,3 +295,64 @@ def test_transformer_workspace_layout_is_pinned():
         assert (lib.opp_object_prefix_bytes(ctx, 5000), lib.opp_object_prefix_workspace_bytes(ctx, 5000)) == PREFIX_BYTES_N5000
     finally:
         lib.opp_destroy(ctx)
+
+
+# (H, W) -> opp_backbone_workspace_bytes, opp_forward_coarse_workspace_bytes at n = 150 / 5000 as (fpn_overlap 0, fpn_overlap 1) each,
+# opp_backbone_fine_branch_workspace_bytes, opp_fine_patch_buffer_floats (which = 0, 1) of the default configuration, recorded from
+# the build of commit 88bd034 (one backbone_impl behind a phase number; the fine-branch size a formula beside its buffers)
+BACKBONE_WS = {(64, 96): (42746112, ((43097344, 45098496), (48063744, 87397888)), 19530752, (196608, 86016)),
+               (136, 104): (54714112, ((55321344, 58286080), (60287744, 100585472)), 23114752, (452608, 198016)),
+               (512, 512): (425722112, ((434265344, 467033600), (439231744, 509332992)), 134218752, (8388608, 3670016))}
+# the first two once more with OPP_ASP=1 in the environment (the plan adds the pre-split twins), same build
+BACKBONE_WS_ASP = {(64, 96): (49602816, ((49954048, 51955200), (54920448, 94254592))),
+                   (136, 104): (70498816, ((71106048, 74070784), (76072448, 116370176))),
+                   (512, 512): (718274816, ((726818048, 759586304), (731784448, 801885696)))}
+BACKBONE_WS_N = (150, 5000)
+
+
+def _backbone_ws_sizes():
+    """{(H, W): sizes in the layout of BACKBONE_WS} from the library as the environment of THIS process configures it"""
+    import ctypes
+    from onepose_plus_plus_amd import _lib
+    lib = _lib.load()
+    ctxs = []
+    try:
+        for overlap in (False, True):
+            ccfg = OnePosePlus_model(default_config()).set_fpn_overlap(overlap)._c_config()
+            assert ccfg.fpn_overlap == int(overlap)
+            ctxs.append(ctypes.c_void_p())
+            _lib.check(lib.opp_create(ctypes.byref(ccfg), ctypes.byref(ctxs[-1])), "opp_create")
+        c0, c1 = ctxs
+        return {hw: (lib.opp_backbone_workspace_bytes(c1, *hw),
+                     tuple((lib.opp_forward_coarse_workspace_bytes(c0, *hw, n), lib.opp_forward_coarse_workspace_bytes(c1, *hw, n))
+                           for n in BACKBONE_WS_N),
+                     lib.opp_backbone_fine_branch_workspace_bytes(c1, *hw),
+                     (lib.opp_fine_patch_buffer_floats(c1, *hw, 0), lib.opp_fine_patch_buffer_floats(c1, *hw, 1)))
+                for hw in BACKBONE_WS}
+    finally:
+        for ctx in ctxs:
+            lib.opp_destroy(ctx)
+
+
+def test_backbone_workspace_sizes_are_pinned():
+    """The workspace of the eval-mode backbone, of the fused coarse call (with and without the fine branch beside the coarse level), of
+    the fine branch completed afterwards and the caller's x1 / x2_out buffers are host arithmetic over one plan per entry: none of
+    them may move (the callers allocate by these numbers and the stages carve the same buffers out of them)."""
+    assert _backbone_ws_sizes() == BACKBONE_WS
+
+
+def test_backbone_workspace_sizes_are_pinned_with_presplit_twins():
+    """OPP_ASP=1 is read by the plan, per call, from the environment: a child process started with it reports the sizes with the
+    pre-split twins (backbone and fused coarse call; the other entries plan no twins and stay as above)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, %r); from tests import test_host_logic as T; "
+            "print(json.dumps([[list(k), v] for k, v in T._backbone_ws_sizes().items()]))" % root)
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, OPP_ASP="1"), cwd=root, capture_output=True, text=True, check=True)
+    got = {tuple(k): v for k, v in json.loads(out.stdout.strip().splitlines()[-1])}
+    for hw, (backbone, coarse) in BACKBONE_WS_ASP.items():
+        assert (got[hw][0], tuple(tuple(c) for c in got[hw][1])) == (backbone, coarse), hw
+        assert (got[hw][2], tuple(got[hw][3])) == BACKBONE_WS[hw][2:], hw
