@@ -87,7 +87,7 @@ __device__ __forceinline__ void opp_store_split4(void* base, size_t row_bytes_of
 // per 32-k chunk and wave, profiles/r06_pmc_conv_*.txt) and no 8-byte LDS stores (a quarter of the LDS cycles were their bank conflicts).
 // (The body is a device function with two kernel entries -- opp_gemm_kernel<..., PREC> and opp_gemm_asp_kernel<..., PREC> -- so that the
 // symbol names of the default kernels, which every profile under profiles/ is keyed by, do not change with the opt-in variant.)
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV, int ABL, int DEPTH, int PREC, bool ASP>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV, int ABL, int DEPTH, int PREC, bool ASP, bool KFOLD = false>
 __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
   constexpr bool H2 = PREC == OPP_PREC_FP16X2;   // operands as hi+lo fp16 pairs, 3 fp16 MFMA products
   constexpr bool H3 = PREC == OPP_PREC_BF16X3;   // operands as hi+mid+lo bf16 triples (exact), 6 bf16 MFMA products
@@ -966,9 +966,35 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
       read_b16(0, std::integral_constant<int, 0>{});
     }
     loop_start();
-    for (int c = 0; c < nk; c += 2) {
-      chunk_m16(std::integral_constant<int, 0>{}, c & 1);
-      chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1);
+    if constexpr (KFOLD) {
+      // g.k_fold equal slices of an even number of chunks (launcher), each summed from zero as its own K-slice launch would, the slice sums
+      // added in slice order like splitk_epilogue_kernel: ((p0 + p1) + p2) + p3, plain fp32 adds.  The cursor, the global prefetch and the
+      // LDS buffer parity run straight across the slice boundaries.
+      f32x4 tot4[MBW][NBWW];
+      const int nks = nk / g.k_fold;
+      for (int s = 0; s < g.k_fold; ++s) {
+        for (int c = 0; c < nks; c += 2) {
+          chunk_m16(std::integral_constant<int, 0>{}, 0);
+          chunk_m16(std::integral_constant<int, 1>{}, 1);
+        }
+#pragma unroll
+        for (int i = 0; i < MBW; ++i)
+#pragma unroll
+          for (int j = 0; j < NBWW; ++j) {
+            if (s == 0) tot4[i][j] = acc4[i][j];
+            else tot4[i][j] += acc4[i][j];
+            acc4[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+#pragma unroll
+      for (int i = 0; i < MBW; ++i)
+#pragma unroll
+        for (int j = 0; j < NBWW; ++j) acc4[i][j] = tot4[i][j];
+    } else {
+      for (int c = 0; c < nk; c += 2) {
+        chunk_m16(std::integral_constant<int, 0>{}, c & 1);
+        chunk_m16(std::integral_constant<int, 1>{}, (c + 1) & 1);
+      }
     }
     if (ABL == 9 || ABL > 90) ts2 = __builtin_readcyclecounter();
     if (g.out_mul != 1.f || g.out_div != 1.f) {                 // output scaling once, in place
@@ -1297,40 +1323,76 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
         continue;
       }
     }
-    for (int u = tid; u < BM * (WP / 4); u += NT) {
-      const int lr = u / (WP / 4);
-      const int lc = (u - lr * (WP / 4)) * 4;
+    // ---- store loop: + bias, + residual, activation, 16 B per lane ----
+    // A thread takes its items kEB at a time: first the global loads of the whole batch (bias, residual taps), then the arithmetic and
+    // the stores.  g.C, g.R and g.bias are plain pointers, so no load may rise above a store that precedes it in program order; item by
+    // item every load was waited for behind the previous item's store, and such a wait also covers that store's round trip to L2 (see
+    // epi_batches): 8 / 16 round trips in a row for the 128 x 128 / 256 x 128 tile, in batches one per batch.
+    // Reading R ahead of the thread's own earlier stores is valid because R is either disjoint from C or the very same map (the
+    // launcher refuses anything else), where a thread reads only what it writes later itself.  Per value the order of the arithmetic is
+    // unchanged: staged value, + bias, + residual, activation, split copy.
+    constexpr int kRowQ = WP / 4;                            // float4 items per staged row
+    constexpr int kUnits = BM * kRowQ;
+    constexpr int kPerThread = (kUnits + NT - 1) / NT;
+    // items per batch: 4, and 2 with the bilinear residual, whose four taps per item would otherwise cost the small tiles a resident
+    // workgroup in registers (tools/isa_audit.py)
+    constexpr int kEB = kPerThread < 4 ? kPerThread : 4, kEBil = kPerThread < 2 ? kPerThread : 2;
+    constexpr bool kColFixed = NT % kRowQ == 0;              // u += NT keeps the column: one bias load per thread
+    typedef float vf4 __attribute__((ext_vector_type(4)));   // (native vectors: the batch stays in registers)
+    struct EpiItem {
+      int row, col;
+      bool ok;
+      vf4 cv, bv, rd, r[4];      // staged value, bias, direct residual, bilinear taps
+      float wx0, wx1, wy0, wy1, rm;
+    };
+    // The loop is instantiated per epilogue shape, chosen by wave-uniform branches outside it: 16-byte or scalar accesses (vec_c), the
+    // residual mode (m_c: kRNone / kRDirect / kRBil), and whether an item loads anything
+    // from global memory at all (w_c).  Inside an instance the mode is a constant: every residual address is visibly g.R + offset (a
+    // global_load, not a flat one, which would also count on lgkmcnt and be waited for by the next item's LDS read), nothing is turned
+    // into an unconditional add behind a select, and the instance without loads has no wait in it.
+    constexpr int kRNone = 0, kRDirect = 1, kRBil = 2;
+    auto ld4 = [&](auto vec_c, const float* p, int nval) __attribute__((always_inline)) -> vf4 {   // nval < 4 only on the scalar path (zeros behind the last stored column)
+      if constexpr (decltype(vec_c)::value) return *reinterpret_cast<const vf4*>(p);
+      return vf4{p[0], nval > 1 ? p[1] : 0.f, nval > 2 ? p[2] : 0.f, nval > 3 ? p[3] : 0.f};
+    };
+    auto epi_col = [&](int lc, int& col) __attribute__((always_inline)) -> bool {         // output column of staged column lc; false: nothing to store there
       const int wn2 = lc / (JP * 32);
       const int j = ps * JP + (lc - wn2 * JP * 32) / 32;
-      const int row = m0 + lr;
-      const int col = kM16 ? n0 + lc : n0 + wn2 * TN * 32 + j * 32 + (lc & 31);
-      if ((!kM16 && (j >= TN || (kRagged && wn2 * TN + j >= NT32))) || row >= g.M || col >= g.n_store) continue;
-      const float4 cv = *reinterpret_cast<const float4*>(Cs + lr * CS + lc);
-      float v[4] = {cv.x, cv.y, cv.z, cv.w};
-      const int nval = g.n_store - col < 4 ? g.n_store - col : 4;   // < 4 only on the scalar path
-      if (g.bias) {
-        if (vec_ok) {
-          const float4 bv = *reinterpret_cast<const float4*>(g.bias + col);
-          v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
-        } else {
-          for (int e = 0; e < nval; ++e) v[e] += g.bias[col + e];
-        }
+      col = kM16 ? n0 + lc : n0 + wn2 * TN * 32 + j * 32 + (lc & 31);
+      return !((!kM16 && (j >= TN || (kRagged && wn2 * TN + j >= NT32))) || col >= g.n_store);
+    };
+    vf4 bias_t = vf4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (kColFixed) {
+      int col;
+      if (g.bias && epi_col((tid % kRowQ) * 4, col)) bias_t = vec_ok ? ld4(std::true_type{}, g.bias + col, 4) : ld4(std::false_type{}, g.bias + col, g.n_store - col);
+    }
+    const bool row_masked = g.act == OPP_ACT_QKV && g.row_mask != nullptr;
+    auto epi_load = [&](auto vec_c, auto m_c, int u, EpiItem& it) __attribute__((always_inline)) {
+      constexpr int M = decltype(m_c)::value;
+      constexpr bool direct = M == kRDirect, bilinear = CONV && M == kRBil;
+      it.ok = false;
+      if (u >= kUnits) return;
+      const int lr = u / kRowQ;
+      const int lc = (u - lr * kRowQ) * 4;
+      it.row = m0 + lr;
+      if (!epi_col(lc, it.col) || it.row >= g.M) return;
+      it.ok = true;
+      const int nval = g.n_store - it.col < 4 ? g.n_store - it.col : 4;
+      it.cv = *reinterpret_cast<const vf4*>(Cs + lr * CS + lc);
+      if constexpr (!kColFixed) {
+        if (g.bias) it.bv = ld4(vec_c, g.bias + it.col, nval);
       }
-      if (g.res_mode == OPP_RES_DIRECT) {
-        const float* rp = g.R + (size_t)row * g.ldr + col;
-        if (vec_ok) {
-          const float4 rv = *reinterpret_cast<const float4*>(rp);
-          v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
-        } else {
-          for (int e = 0; e < nval; ++e) v[e] += rp[e];
-        }
-      } else if (g.res_mode == OPP_RES_BILINEAR2X) {
+      if (row_masked && it.row < g.row_mask_rows) it.rm = g.row_mask[it.row];
+      // (every field of the batch is written at ONE place: stores to one field in sibling branches would be merged into a store through
+      // a selected address, and the batch would then live in scratch -- hence rd beside r[0])
+      if (direct) it.rd = ld4(vec_c, g.R + (size_t)it.row * g.ldr + it.col, nval);
+      if (bilinear) {
         // bilinear x2 (align_corners=True) taps of the half-resolution residual (resnet.py:151,155).
         // No FMA contraction in this block: the compiler fuses differently in different tile instantiations, and
         // every tile shape must produce the same bits (tools/tile_invariance_check.py).
 #pragma clang fp contract(off)
-        const int ox = row % g.Wout;
-        const int t = row / g.Wout;
+        const int ox = it.row % g.Wout;
+        const int t = it.row / g.Wout;
         const int oy = t % g.Hout;
         const int b = t / g.Hout;
         const float sy = g.res_sy * (float)oy;
@@ -1341,34 +1403,40 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
         if (x0 > g.Wr - 1) x0 = g.Wr - 1;
         const int y1 = y0 + (y0 < g.Hr - 1 ? 1 : 0);
         const int x1 = x0 + (x0 < g.Wr - 1 ? 1 : 0);
-        const float wy1 = fminf(fmaxf(sy - (float)y0, 0.f), 1.f);
-        const float wx1 = fminf(fmaxf(sx - (float)x0, 0.f), 1.f);
-        const float wy0 = 1.f - wy1, wx0 = 1.f - wx1;
+        it.wy1 = fminf(fmaxf(sy - (float)y0, 0.f), 1.f);
+        it.wx1 = fminf(fmaxf(sx - (float)x0, 0.f), 1.f);
+        it.wy0 = 1.f - it.wy1;
+        it.wx0 = 1.f - it.wx1;
         const int pb = b * g.Hr * g.Wr;
-        const float* r00 = g.R + (size_t)(pb + y0 * g.Wr + x0) * g.ldr + col;
-        const float* r01 = g.R + (size_t)(pb + y0 * g.Wr + x1) * g.ldr + col;
-        const float* r10 = g.R + (size_t)(pb + y1 * g.Wr + x0) * g.ldr + col;
-        const float* r11 = g.R + (size_t)(pb + y1 * g.Wr + x1) * g.ldr + col;
-        float a00[4], a01[4], a10[4], a11[4];
-        if (vec_ok) {
-          const float4 t0 = *reinterpret_cast<const float4*>(r00), t1 = *reinterpret_cast<const float4*>(r01);
-          const float4 t2 = *reinterpret_cast<const float4*>(r10), t3 = *reinterpret_cast<const float4*>(r11);
-          a00[0] = t0.x; a00[1] = t0.y; a00[2] = t0.z; a00[3] = t0.w;
-          a01[0] = t1.x; a01[1] = t1.y; a01[2] = t1.z; a01[3] = t1.w;
-          a10[0] = t2.x; a10[1] = t2.y; a10[2] = t2.z; a10[3] = t2.w;
-          a11[0] = t3.x; a11[1] = t3.y; a11[2] = t3.z; a11[3] = t3.w;
-        } else {
-          for (int e = 0; e < 4; ++e) {
-            const bool ok = e < nval;
-            a00[e] = ok ? r00[e] : 0.f; a01[e] = ok ? r01[e] : 0.f;
-            a10[e] = ok ? r10[e] : 0.f; a11[e] = ok ? r11[e] : 0.f;
-          }
-        }
+        it.r[0] = ld4(vec_c, g.R + (size_t)(pb + y0 * g.Wr + x0) * g.ldr + it.col, nval);
+        it.r[1] = ld4(vec_c, g.R + (size_t)(pb + y0 * g.Wr + x1) * g.ldr + it.col, nval);
+        it.r[2] = ld4(vec_c, g.R + (size_t)(pb + y1 * g.Wr + x0) * g.ldr + it.col, nval);
+        it.r[3] = ld4(vec_c, g.R + (size_t)(pb + y1 * g.Wr + x1) * g.ldr + it.col, nval);
+      }
+    };
+    auto epi_finish = [&](auto vec_c, auto m_c, auto w_c, const EpiItem& it) __attribute__((always_inline)) {
+      constexpr int M = decltype(m_c)::value;
+      constexpr bool direct = M == kRDirect, bilinear = CONV && M == kRBil;
+      if (!it.ok) return;
+      const int row = it.row, col = it.col;
+      const int nval = g.n_store - col < 4 ? g.n_store - col : 4;
+      float v[4] = {it.cv.x, it.cv.y, it.cv.z, it.cv.w};
+      if (g.bias) {
+        const vf4 bv = kColFixed ? bias_t : it.bv;
+        v[0] += bv.x; v[1] += bv.y; v[2] += bv.z; v[3] += bv.w;
+      }
+      if (direct) {
+        const vf4 rv = it.rd;
+        v[0] += rv.x; v[1] += rv.y; v[2] += rv.z; v[3] += rv.w;
+      } else if (bilinear) {
+#pragma clang fp contract(off)
+        const float a00[4] = {it.r[0].x, it.r[0].y, it.r[0].z, it.r[0].w}, a01[4] = {it.r[1].x, it.r[1].y, it.r[1].z, it.r[1].w};
+        const float a10[4] = {it.r[2].x, it.r[2].y, it.r[2].z, it.r[2].w}, a11[4] = {it.r[3].x, it.r[3].y, it.r[3].z, it.r[3].w};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float top = wx0 * a00[e] + wx1 * a01[e];
-          const float bot = wx0 * a10[e] + wx1 * a11[e];
-          v[e] += wy0 * top + wy1 * bot;
+          const float top = it.wx0 * a00[e] + it.wx1 * a01[e];
+          const float bot = it.wx0 * a10[e] + it.wx1 * a11[e];
+          v[e] += it.wy0 * top + it.wy1 * bot;
         }
       }
       if (g.act == OPP_ACT_RELU) {
@@ -1386,22 +1454,59 @@ __device__ __forceinline__ void opp_gemm_body(const OppGemm& g) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = v[e] / vdiv;
         }
-        if (g.row_mask != nullptr && row < g.row_mask_rows) {   // padded image tokens: Q, K, V rows -> 0 (linear_attention.py:49-53)
-          const float rm = g.row_mask[row];
+        if constexpr (decltype(w_c)::value) {   // (a masked launch never takes the instance without loads)
+          if (row_masked && row < g.row_mask_rows) {   // padded image tokens: Q, K, V rows -> 0 (linear_attention.py:49-53); loaded by epi_load
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= rm;
+            for (int e = 0; e < 4; ++e) v[e] *= it.rm;
+          }
         }
       }
       if constexpr (H3) {    // the same values once more, pre-split for the convolutions that consume this map (launcher: vec_ok, no K slices)
         if (g.C3 != nullptr) opp_store_split4(g.C3, (size_t)row * g.ld3, col, make_float4(v[0], v[1], v[2], v[3]));
       }
-      if (g.C == nullptr) continue;       // split output only
+      if (g.C == nullptr) return;         // split output only
       float* cp = g.C + (size_t)row * g.ldc + col + (g.k_splits > 1 ? (size_t)blockIdx.y * g.split_stride : 0);
-      if (vec_ok) {
+      if constexpr (decltype(vec_c)::value) {
         *reinterpret_cast<float4*>(cp) = make_float4(v[0], v[1], v[2], v[3]);
       } else {
         for (int e = 0; e < nval; ++e) cp[e] = v[e];
       }
+    };
+    // vmcnt counts stores as well as loads and retires in order, so a wait for a load that is placed behind a store also waits for that
+    // store's acknowledgement from L2 -- the round trip per item that this loop is rid of (measured: DESIGN.md 4.1).  So the waits are
+    // stated here, where no store of the batch precedes them, and the compiler has none left to place between the stores: ONE per batch
+    // for the batch's loads (vmcnt 0; expcnt, lgkmcnt untouched), and where the items load nothing (no residual, the thread's one bias
+    // value, no row mask) one in front of the loop for that bias value and none in it.
+    // s_waitcnt immediate, gfx9 layout: vmcnt = bits [3:0] and [15:14] = 0; expcnt [6:4] = 7 and lgkmcnt [11:8] = 15, i.e. not waited for
+    constexpr int kWaitVm0 = 0x0F70;
+    auto epi_batches = [&](auto vec_c, auto eb_c, auto m_c, auto w_c) __attribute__((always_inline)) {
+      constexpr int EB = decltype(eb_c)::value;
+      constexpr bool W = decltype(w_c)::value;
+      if constexpr (!W) __builtin_amdgcn_s_waitcnt(kWaitVm0);
+      for (int ub = tid; ub < kUnits; ub += NT * EB) {
+        EpiItem it[EB];
+#pragma unroll
+        for (int b = 0; b < EB; ++b) epi_load(vec_c, m_c, ub + b * NT, it[b]);
+        if constexpr (W) __builtin_amdgcn_s_waitcnt(kWaitVm0);
+#pragma unroll
+        for (int b = 0; b < EB; ++b) epi_finish(vec_c, m_c, w_c, it[b]);
+      }
+    };
+    using EpiB = std::integral_constant<int, kEB>;
+    using One = std::integral_constant<int, 1>;
+    const bool bil = CONV && g.res_mode == OPP_RES_BILINEAR2X, dir = g.res_mode == OPP_RES_DIRECT;
+    if (!vec_ok) {   // odd widths and strides (tests, tools): item by item
+      if (bil) epi_batches(std::false_type{}, One{}, std::integral_constant<int, kRBil>{}, std::true_type{});
+      else if (dir) epi_batches(std::false_type{}, One{}, std::integral_constant<int, kRDirect>{}, std::true_type{});
+      else epi_batches(std::false_type{}, One{}, std::integral_constant<int, kRNone>{}, std::true_type{});
+    } else if (bil) {
+      epi_batches(std::true_type{}, std::integral_constant<int, kEBil>{}, std::integral_constant<int, kRBil>{}, std::true_type{});
+    } else if (dir) {
+      epi_batches(std::true_type{}, EpiB{}, std::integral_constant<int, kRDirect>{}, std::true_type{});
+    } else if (!kColFixed || row_masked) {
+      epi_batches(std::true_type{}, EpiB{}, std::integral_constant<int, kRNone>{}, std::true_type{});
+    } else {
+      epi_batches(std::true_type{}, EpiB{}, std::integral_constant<int, kRNone>{}, std::false_type{});
     }
   }
   if ((ABL == 9 || ABL > 90) && g.dbg_ts != nullptr && lane == 0) {
@@ -1420,6 +1525,12 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void opp_gemm_kernel(const O
 template <int BM, int BN, int WAVES_M, int WAVES_N, int ABL = 0, int DEPTH = 2, int PREC = OPP_PREC_BF16X3>
 __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void opp_gemm_asp_kernel(const OppGemm g) {
   opp_gemm_body<BM, BN, WAVES_M, WAVES_N, true, ABL, DEPTH, PREC, true>(g);
+}
+
+// the K slices of a convolution summed inside the workgroup (g.k_fold; 128 x 128 on 8 waves, bf16x3): the one instance that pays for a second
+// accumulator set
+__global__ __launch_bounds__(512) void opp_gemm_kfold_kernel(const OppGemm g) {
+  opp_gemm_body<128, 128, 4, 2, true, 0, 2, OPP_PREC_BF16X3, false, true>(g);
 }
 
 // out = act(sum_s part[s] + bias + R): the split-K slices of a convolution summed in slice order (deterministic), then the epilogue
@@ -1638,6 +1749,10 @@ bool opp_conv_splitk_by_shape(long long M, int n_store, int K) {
   const long long tiles128 = ((M + 127) / 128) * (long long)opp_cdiv(n_store, 128);
   return tiles128 <= 64 && K / 32 >= 32;
 }
+static bool conv_kfold_off() {
+  const char* v = getenv("OPP_CONV_KFOLD");
+  return v && v[0] == '0';
+}
 static bool splitk_by_shape(const OppGemm& g) { return opp_conv_splitk_by_shape(g.M, g.n_store, g.K); }
 
 // The launcher's own tile choice (tile_cfg < 0) as a pure function of the problem shape, the operand arithmetic and the tile policy:
@@ -1786,6 +1901,19 @@ int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
     OPP_CHECK_ARG(g.ksplit % 32 == 0 && (g.ksplit >= g.K || g.A1), "gemm: bad ksplit");
     OPP_CHECK_ARG(g.res_mode != OPP_RES_BILINEAR2X, "gemm: bilinear residual needs conv mode");
   }
+  if (g.res_mode != OPP_RES_NONE) {
+    // the store loop loads a batch of residual values ahead of its own stores (opp_gemm_body): R is the output map itself -- a thread then
+    // reads only what it writes later -- or lies apart from everything the kernel writes
+    const size_t r_rows = g.res_mode == OPP_RES_BILINEAR2X ? (size_t)g.Bn * g.Hr * g.Wr : (size_t)g.M;
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(g.R), r1 = r0 + ((r_rows - 1) * (size_t)g.ldr + g.n_store) * 4;
+    auto apart = [&](const void* p, size_t bytes) {
+      const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
+      return p == nullptr || r1 <= p0 || p0 + bytes <= r0;
+    };
+    const bool same_map = g.res_mode == OPP_RES_DIRECT && g.R == g.C && g.ldr == g.ldc;
+    OPP_CHECK_ARG(same_map || apart(g.C, ((size_t)(g.M - 1) * g.ldc + g.n_store) * 4), "gemm: the residual's byte span overlaps the output's without being the same map (column slices of one buffer interleaved by the row stride count as overlapping)");
+    OPP_CHECK_ARG(apart(g.C3, (size_t)(g.M - 1) * g.ld3 + (size_t)g.n_store * 6), "gemm: the residual overlaps the pre-split output");
+  }
   if (g.k_splits > 1) {
     OPP_CHECK_ARG(g.k_chunks_per_split > 0 && (long long)g.k_splits * g.k_chunks_per_split * 32 >= g.K && g.split_stride >= (size_t)g.M * g.ldc,
                   "gemm: bad split-K description (%d splits x %d chunks for K %d)", g.k_splits, g.k_chunks_per_split, g.K);
@@ -1802,6 +1930,22 @@ int opp_gemm_launch_cfg(const OppGemm& g_in, int cfg, hipStream_t stream) {
     const size_t need = (size_t)kSplits * g.M * g.ldc;
     const bool by_shape = splitk_by_shape(g);
     if ((g.splitk_force > 0 || (g.splitk_force < 0 && by_shape)) && nkc >= kSplits && g.splitk_ws_floats >= need && need < (1ull << 31)) {
+      // several forwards in flight: the other forwards fill the chip, so the slices only buy 256 prologues and epilogues instead of 64, a
+      // round trip of partials and a launch.  Four equal slices of an even number of chunks (K / 32 a multiple of 8) are then summed inside
+      // ONE workgroup per tile: the same bits (tests/test_conv_kfold_gpu.py).  Odd or ragged slices, pre-split input (that instance is
+      // not built) and the latency policy keep the slices.  OPP_CONV_KFOLD=0: the A/B switch of the tools, read on every call.
+      if (g.tile_policy == OPP_TILES_THROUGHPUT && nkc % (2 * kSplits) == 0 && !g.a_split && !conv_kfold_off()) {
+        OppGemm gf = g;
+        gf.k_fold = kSplits;
+        gf.splitk_ws = nullptr;
+        const size_t lds = (size_t)2 * (128 + 128) * lds_stride(OPP_PREC_BF16X3) * sizeof(float);
+        static OppLdsOnce attr_done;
+        set_lds_once(opp_gemm_kfold_kernel, lds, attr_done);
+        OppProfScope prof_fold(OPP_PROF_CONV_SPLITK, stream, g.alg_flops > 0.0 ? g.alg_flops : 2.0 * (double)g.M * (double)g.N * (double)g.K);
+        hipLaunchKernelGGL(opp_gemm_kfold_kernel, dim3(opp_cdiv(g.M, 128) * opp_cdiv(g.n_store, 128)), dim3(512), lds, stream, gf);
+        OPP_CHECK_LAUNCH("opp_gemm_kfold_kernel");
+        return OPP_OK;
+      }
       OppGemm gs = g;
       gs.C = g.splitk_ws;
       gs.C3 = nullptr;              // the K slices are fp32 partials; the fixed-order epilogue below emits the split copy

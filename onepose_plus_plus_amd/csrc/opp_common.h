@@ -158,6 +158,9 @@ struct OppGemm {
   int k_splits = 1;
   int k_chunks_per_split = 0;
   size_t split_stride = 0;
+  // bf16x3 convolution on the 128 x 128 tile, set by the launcher only: k_fold > 1 -> ONE workgroup per tile walks all of K as k_fold equal
+  // slices and sums the slice accumulators in slice order in registers (the bits of the K slices + splitk_epilogue_kernel)
+  int k_fold = 0;
   // conv mode, automatic tile choice: scratch for split-K partial products (>= 4 * M * ldc floats).  When given, a convolution whose
   // output is at most 64 tiles of 128 x 128 under a K of >= 32 chunks (the 3x3 convolutions of the 1/8-resolution stage at B = 1:
   // 4096 pixels x 256 channels x K = 2304) runs as 4 K slices on 8-wave 128 x 128 tiles -- 256 workgroups instead of 64 .. 256

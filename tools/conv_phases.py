@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from onepose_plus_plus_amd import _lib  # noqa: E402
 
-CASES = [("layer1 3x3 128->128 @256", 256, 256, 128, 128, 3, 1), ("l2_out2a 3x3 256->256 @128", 128, 128, 256, 256, 3, 1)]
+CASES = [("layer1 3x3 128->128 @256", 256, 256, 128, 128, 3, 1), ("l2_out2a 3x3 256->256 @128", 128, 128, 256, 256, 3, 1),
+         ("layer3 3x3 256->256 @64", 64, 64, 256, 256, 3, 1)]
 
 
 def main():
