@@ -548,6 +548,39 @@ int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, cons
                       int* n_inliers, int* ok, int* stop_out, int* samples_out, int* scores_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* LO-RANSAC with robust refinement: the reference's pycolmap branch (pycolmap.absolute_pose_estimation, i.e. COLMAP 3.8
+ * EstimateAbsolutePose: LORANSAC<P3PEstimator, EPNPEstimator>, then RefineAbsolutePose under a Cauchy loss).  Trial t draws 3
+ * matches (the sampler of opp_pnp_ransac), P3P gives 0..4 models and every one is scored: support = (inliers, sum of their
+ * squared reprojection errors), inlier = error <= reproj_error_px^2 in front of the camera, better = more inliers or as many and a
+ * smaller sum.  A model that beats the best support with more than 4 inliers is locally optimised (EPnP on the best model's
+ * inliers, repeated while the inlier count grows, at most 10 times).  After every new best dyn = ceil(3 log(1 - confidence) /
+ * log(1 - r^3)), r = inliers / n; the loop ends at the first trial >= dyn and >= min_trials, `iterations` at the latest
+ * (confidence >= 1: never earlier).  The best model's inliers are the ones returned; the pose is refined on them by
+ * Levenberg-Marquardt on sum log(1 + error) (a step is taken only when that cost falls, <= 100 iterations, stop at
+ * |gradient|_inf <= 1).  The points are not rescaled; K4 =
+ * {fx, fy, cx, cy} on the host (the reference's SIMPLE_PINHOLE camera: pass fy = fx).  Failure (identity pose, ok = 0, empty mask):
+ * n < 3, no model, or a best inlier count of 0 or below min_inlier_ratio * n.  All trials run in parallel; the result is that of the
+ * sequential loop.  stop_out (may be NULL): trials the sequential loop runs.  `record` (may be NULL, any member may be NULL):
+ * device buffers for what the run decided on; entries of trials past the stop bound are left as they were. */
+typedef struct OppLoRecord {
+  int* samples;        /* [iterations][3] match indices of every trial */
+  int* counts;         /* [iterations][4] inliers of every model, -1 = no such model */
+  double* sums;        /* [iterations][4] residual sum of its inliers */
+  double* models;      /* [iterations][4][12] the models, row-major [R | t] as 9 + 3 */
+  int* n_cand;         /* 1: models whose support beats every earlier model's (the only ones LO can run on) */
+  int* cand_idx;       /* [iterations * 4] 4 * trial + model of each, ascending */
+  int* cand_cnt;       /* [iterations * 4] support after local optimisation */
+  double* cand_sum;
+  int* cand_taken;     /* [iterations * 4] 1 = became the best in the sequential loop; the last one taken is the result */
+  double* ransac_pose; /* [12] row-major 3x4 pose before the refinement */
+  int* lm_iters;       /* 1: damped systems the refinement solved */
+} OppLoRecord;
+size_t opp_pnp_loransac_workspace_bytes(int iterations, int n_points);
+int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_points, const double* K4,
+                     double reproj_error_px, int iterations, unsigned seed, double confidence, int min_trials,
+                     double min_inlier_ratio, double* pose_out, int* inlier_mask, int* n_inliers, int* ok,
+                     int* stop_out, const OppLoRecord* record, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Tuning aid (libraries built with -DOPP_TUNING only; otherwise returns an error): device buffer (4 x uint64 per
  * wave) for the phase time stamps written by the timed conv variants (tile_cfg 120 = 256x128 / 8 waves,
  * 121 = 128x128 / 4 waves, 122 = 128x128 / 8 waves); NULL disables. */

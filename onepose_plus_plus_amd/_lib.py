@@ -48,6 +48,12 @@ class OppConfig(Structure):
     ]
 
 
+class OppLoRecord(Structure):
+    """optional device outputs of opp_pnp_loransac (include/opp_hip.h); NULL members are skipped"""
+    _fields_ = [(k, c_void_p) for k in ("samples", "counts", "sums", "models", "n_cand", "cand_idx", "cand_cnt", "cand_sum",
+                                        "cand_taken", "ransac_pose", "lm_iters")]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/opp_hip.h
 # (tests/test_cabi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -153,6 +159,10 @@ SIGNATURES = {
     "opp_pnp_ransac_ex": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
                                   c_int, ctypes.c_uint, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "opp_pnp_loransac_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "opp_pnp_loransac": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, c_int, ctypes.c_uint,
+                                 ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_size_t, c_void_p]),
     "opp_backbone_tape_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "opp_backbone_train_tape_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "opp_backbone_train_tape": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -22,25 +22,9 @@
 //                   the best hypothesis's inlier mask, and an EPnP refit on those inliers (reductions in point order)
 #include "opp_common.h"
 #include "pnp_math.h"
+#include "pnp_sample.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned hash32(unsigned x) {
-  x ^= x >> 16;
-  x *= 0x7feb352du;
-  x ^= x >> 15;
-  x *= 0x846ca68bu;
-  x ^= x >> 16;
-  return x;
-}
-
-struct PnpParams {
-  double K4[4];   // fx, fy, cx, cy
-  double thr2;    // squared reprojection threshold (px^2)
-  double scale;   // world-point scale (reference: configs["point_cloud_rescale"])
-  int n, iters;
-  unsigned seed;
-};
 
 __global__ __launch_bounds__(256) void pnp_hypotheses_kernel(const float* __restrict__ p2, const float* __restrict__ p3,
                                                              PnpParams prm, double* __restrict__ hyp, int* __restrict__ valid) {
@@ -244,24 +228,6 @@ __global__ __launch_bounds__(256) void pnp_refine_kernel(const float* __restrict
 
 
 // ---- EPnP (opp_pnp_ransac_ex, solver 1) ------------------------------------------------------------------------------
-
-// the sampling of pnp_hypotheses_kernel, drawing K distinct indices
-template <int K>
-__device__ __forceinline__ void draw_sample(unsigned seed, int h, int n, int* idx) {
-  unsigned s = hash32(seed ^ (0x9e3779b9u * (unsigned)(h + 1)));
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    for (int tries = 0; tries < 64; ++tries) {
-      s = hash32(s + 0x632be5abu);
-      const int c = (int)(s % (unsigned)n);
-      bool dup = false;
-#pragma unroll
-      for (int j = 0; j < k; ++j) dup |= idx[j] == c;
-      idx[k] = c;
-      if (!dup) break;
-    }
-  }
-}
 
 // sample indices of the P3P hypotheses (4 per hypothesis, the 5th column -1), for opp_pnp_ransac_ex's optional output
 __global__ __launch_bounds__(256) void pnp_p3p_samples_kernel(PnpParams prm, int* __restrict__ samples) {

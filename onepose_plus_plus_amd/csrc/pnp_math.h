@@ -814,3 +814,248 @@ OPP_HDI int opp_ransac_stop(const int* score, int iters, int n, int m, double co
   *best = b;
   return it;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// LO-RANSAC with robust refinement (COLMAP 3.8 EstimateAbsolutePose: LORANSAC<P3PEstimator, EPNPEstimator>, then
+// RefineAbsolutePose under a Cauchy loss -- the reference's `use_pycolmap_ransac=True` branch, metric_utils.py:137-170).
+// The pieces that decide something -- support order, trial bound, the sequential walk over the candidate models, the
+// Levenberg-Marquardt refinement -- are written once for the device (pnp_lo.hip) and the host (tests/loransac_host.cpp).
+// ---------------------------------------------------------------------------------------------------------------------
+#define OPP_LO_ROUNDS 10          // local optimisations per new best (COLMAP kMaxNumLocalTrials)
+#define OPP_LO_MIN_INLIERS 4      // LO runs with more inliers than this (the EPnP estimator's minimal sample)
+#define OPP_LO_NOSUM 1.7976931348623157e308   // residual sum of "no model yet"
+#define OPP_LM_MAX_ITERS 100
+#define OPP_LM_LAMBDA0 1e-4       // initial damping (Ceres' initial trust-region radius 1e4)
+#define OPP_LM_FACTOR 10.0        // the damping is divided by it after an accepted step, multiplied after a rejected one
+#define OPP_LM_LAMBDA_MIN 1e-12
+#define OPP_LM_LAMBDA_MAX 1e16    // "the damping overflows"
+#define OPP_LM_MIN_GAIN 1e-3      // a step is taken when the cost falls by this fraction of the predicted decrease (Ceres' min_relative_decrease)
+#define OPP_LM_GRAD_TOL 1.0       // COLMAP's gradient_tolerance on the max-norm of the gradient
+#define OPP_LM_ROW 16             // doubles per point: Ju[6], Jv[6], ru, rv, weight, rho
+
+// support (inlier count, sum of the inliers' squared residuals) a is better than b
+OPP_HDI bool opp_support_better(int ca, double sa, int cb, double sb) { return ca > cb || (ca == cb && sa < sb); }
+
+// trials needed so that an all-inlier 3-sample was drawn with probability `confidence`, times COLMAP's multiplier 3:
+// ceil(3 log(1 - confidence) / log(1 - r^3)), r = cnt / n.  confidence >= 1: the cap; r = 1: 0; log(1 - r^3) = 0: the cap.
+OPP_HDI int opp_lo_dyn(double confidence, int cnt, int n, int cap) {
+  OPP_NOFMA
+  if (!(confidence < 1.0)) return cap;
+  if (cnt >= n) return 0;
+  const double r = (double)cnt / n;
+  const double den = log(1.0 - r * r * r);
+  if (!(den < 0.0)) return cap;
+  const double v = 3.0 * log(1.0 - confidence) / den;
+  return v >= (double)cap ? cap : (int)ceil(v);
+}
+
+// The sequential loop over the candidate models.  cand_idx[c] = 4 * trial + model, ascending; (rc, rs)[c] the support of the
+// model itself, (lc, ls)[c] its support after local optimisation (equal to the raw one when LO did not run or did not help).
+// A candidate is taken when the loop has not ended before its trial and its raw support beats the best so far; the best then
+// becomes its LO support and the bound follows.  The loop ends at the first trial t >= dyn and >= min_trials (checked before a
+// trial starts, so the models of the current trial are all seen).  Returns the stop index; *best = the last candidate taken
+// (-1: none); taken[c] (may be NULL) = 1 for the candidates taken.
+OPP_HDI int opp_lo_resolve(const int* cand_idx, const int* rc, const double* rs, const int* lc, const double* ls, int ncand, int n,
+                           double confidence, int min_trials, int cap, int* best, int* taken) {
+  int bc = 0, b = -1, dyn = cap, last = -1;
+  double bs = OPP_LO_NOSUM;
+  bool ended = false;
+  for (int c = 0; c < ncand; ++c) {
+    const int t = cand_idx[c] >> 2;
+    int end = dyn > min_trials ? dyn : min_trials;
+    if (last + 1 > end) end = last + 1;
+    ended = ended || t >= end;
+    const bool live = !ended && opp_support_better(rc[c], rs[c], bc, bs);
+    if (taken) taken[c] = live ? 1 : 0;
+    if (live) {
+      bc = lc[c];
+      bs = ls[c];
+      b = c;
+      last = t;
+      dyn = opp_lo_dyn(confidence, bc, n, cap);
+    }
+  }
+  int end = dyn > min_trials ? dyn : min_trials;
+  if (last + 1 > end) end = last + 1;
+  *best = b;
+  return end < cap ? end : cap;
+}
+
+struct OppLmWs {
+  OppPose P, N;            // the accepted pose, the trial pose
+  double H[36], g[6];      // normal equations at P (H symmetric, H d = g)
+  double A[36], d[6];      // the damped system and its solution
+  double cost, cost_new;   // sum of log(1 + s_i) at P / at N
+  double pred;             // decrease of the cost that the linearised model predicts for the step: d . (g + lambda diag(H) d)
+  double lambda;
+  int iters;               // damped systems solved
+  int done, ok, acc;
+};
+
+// one point of the robust problem at pose P: the Jacobian rows of (u, v) with respect to the update (w, dt) of
+// X_cam' = exp([w]x) (R X + t) + dt, the residual, the first-order Cauchy weight 1 / (1 + s) and rho = log(1 + s), s = |r|^2.
+// A point at or behind the camera gets weight 0 and rho 1e300, so a step that puts one there is rejected.
+OPP_HDI void opp_lm_row(const OppPose& P, const double* K4, const double* X, const double* uv, double* row) {
+  OPP_NOFMA
+  const double xc = P.R[0] * X[0] + P.R[1] * X[1] + P.R[2] * X[2] + P.t[0];
+  const double yc = P.R[3] * X[0] + P.R[4] * X[1] + P.R[5] * X[2] + P.t[1];
+  const double zc = P.R[6] * X[0] + P.R[7] * X[1] + P.R[8] * X[2] + P.t[2];
+  if (!(zc > 1e-12)) {
+    for (int k = 0; k < 15; ++k) row[k] = 0.0;
+    row[15] = 1e300;
+    return;
+  }
+  const double iz = 1.0 / zc;
+  const double ru = K4[0] * xc * iz + K4[2] - uv[0];
+  const double rv = K4[1] * yc * iz + K4[3] - uv[1];
+  const double ju0 = K4[0] * iz, ju2 = -K4[0] * xc * iz * iz;
+  const double jv1 = K4[1] * iz, jv2 = -K4[1] * yc * iz * iz;
+  row[0] = ju2 * yc;
+  row[1] = ju0 * zc - ju2 * xc;
+  row[2] = -ju0 * yc;
+  row[3] = ju0;
+  row[4] = 0.0;
+  row[5] = ju2;
+  row[6] = -jv1 * zc + jv2 * yc;
+  row[7] = -jv2 * xc;
+  row[8] = jv1 * xc;
+  row[9] = 0.0;
+  row[10] = jv1;
+  row[11] = jv2;
+  const double s = ru * ru + rv * rv;
+  row[12] = ru;
+  row[13] = rv;
+  row[14] = 1.0 / (1.0 + s);
+  row[15] = log(1.0 + s);
+}
+
+// entry e of the sums over the rows, in point order: e < 21 the upper triangle of H (row-major), 21..26 g, 27 the cost
+OPP_HDI double opp_lm_sum(const double* rows, int n, int e) {
+  OPP_NOFMA
+  double s = 0.0;
+  if (e == 27) {
+    for (int i = 0; i < n; ++i) s = s + rows[(size_t)i * OPP_LM_ROW + 15];
+    return s;
+  }
+  if (e >= 21) {
+    const int k = e - 21;
+    for (int i = 0; i < n; ++i) {
+      const double* r = rows + (size_t)i * OPP_LM_ROW;
+      s = s - r[14] * (r[k] * r[12] + r[6 + k] * r[13]);
+    }
+    return s;
+  }
+  int a = 0, f = e;
+  while (f >= 6 - a) {
+    f -= 6 - a;
+    ++a;
+  }
+  const int b = a + f;
+  for (int i = 0; i < n; ++i) {
+    const double* r = rows + (size_t)i * OPP_LM_ROW;
+    s = s + r[14] * (r[a] * r[b] + r[6 + a] * r[6 + b]);
+  }
+  return s;
+}
+
+OPP_HDI void opp_lm_store(OppLmWs* w, int e, double v) {
+  if (e >= 21) {
+    w->g[e - 21] = v;
+    return;
+  }
+  int a = 0, f = e;
+  while (f >= 6 - a) {
+    f -= 6 - a;
+    ++a;
+  }
+  w->H[a * 6 + a + f] = v;
+  w->H[(a + f) * 6 + a] = v;
+}
+
+// the damped step from w->P: (H + lambda diag H) d = g, N = the updated pose.  Serial.  False when the system is singular.
+OPP_HDI bool opp_lm_step(OppLmWs* w) {
+  for (int k = 0; k < 36; ++k) w->A[k] = w->H[k];
+  for (int k = 0; k < 6; ++k) {
+    w->A[k * 7] = w->H[k * 7] + w->lambda * w->H[k * 7];
+    w->d[k] = w->g[k];
+  }
+  if (!opp_solve6(w->A, w->d)) return false;
+  for (int k = 0; k < 6; ++k)
+    if (!opp_finite(w->d[k])) return false;
+  double pred = 0.0;
+  for (int k = 0; k < 6; ++k) pred = pred + w->d[k] * (w->g[k] + w->lambda * w->H[k * 7] * w->d[k]);
+  w->pred = pred;
+  w->N = w->P;
+  opp_rot_update(w->N.R, w->d);
+  double E[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  opp_rot_update(E, w->d);
+  for (int r = 0; r < 3; ++r) w->N.t[r] = E[r * 3] * w->P.t[0] + E[r * 3 + 1] * w->P.t[1] + E[r * 3 + 2] * w->P.t[2] + w->d[3 + r];
+  return true;
+}
+
+// accept / reject: the step is taken only when the robust cost decreases, by at least OPP_LM_MIN_GAIN of the predicted decrease
+// (near convergence cost - cost_new is a difference of nearly equal sums; against the prediction the decision stays far from
+// its rounding error, where a bare cost_new < cost would not)
+OPP_HDI void opp_lm_accept(OppLmWs* w) {
+  w->acc = (w->pred > 0.0 && w->cost - w->cost_new > OPP_LM_MIN_GAIN * w->pred) ? 1 : 0;
+  if (w->acc) {
+    w->P = w->N;
+    w->cost = w->cost_new;
+    w->lambda = w->lambda / OPP_LM_FACTOR;
+    if (w->lambda < OPP_LM_LAMBDA_MIN) w->lambda = OPP_LM_LAMBDA_MIN;
+  } else {
+    w->lambda = w->lambda * OPP_LM_FACTOR;
+    if (w->lambda > OPP_LM_LAMBDA_MAX) w->done = 1;
+  }
+}
+
+// Levenberg-Marquardt on sum_i log(1 + |pi(R X_i + t) - uv_i|^2) over the n points X [n][3], uv [n][2], from w->P.
+// rows: n * OPP_LM_ROW doubles.  Every one of the nt threads calls it (it contains barriers); on return w->P is the refined
+// pose, w->iters the damped systems solved, w->cost the robust cost at w->P.  Stops at |g|_inf <= OPP_LM_GRAD_TOL, after
+// OPP_LM_MAX_ITERS iterations or when the damping passes OPP_LM_LAMBDA_MAX.
+OPP_HDI void opp_lm_refine(const double* X, const double* uv, int n, const double* K4, OppLmWs* w, double* rows, int tid, int nt) {
+  if (tid == 0) {
+    w->lambda = OPP_LM_LAMBDA0;
+    w->iters = 0;
+    w->done = 0;
+  }
+  for (int i = tid; i < n; i += nt) opp_lm_row(w->P, K4, X + 3 * (size_t)i, uv + 2 * (size_t)i, rows + (size_t)i * OPP_LM_ROW);
+  OPP_BARRIER();
+  for (int e = tid; e < 28; e += nt) {
+    const double v = opp_lm_sum(rows, n, e);
+    if (e == 27) w->cost = v; else opp_lm_store(w, e, v);
+  }
+  OPP_BARRIER();
+  for (int it = 0; it < OPP_LM_MAX_ITERS; ++it) {
+    if (tid == 0) {
+      double gm = 0.0;
+      for (int k = 0; k < 6; ++k) gm = fmax(gm, fabs(w->g[k]));
+      if (!(gm > OPP_LM_GRAD_TOL)) w->done = 1;
+      if (!w->done) {
+        w->iters = w->iters + 1;
+        w->ok = opp_lm_step(w) ? 1 : 0;
+      }
+    }
+    OPP_BARRIER();
+    const int done = w->done, ok = w->ok;
+    OPP_BARRIER();   // every thread has read them before thread 0 writes again
+    if (done) break;
+    if (ok) {
+      for (int i = tid; i < n; i += nt) opp_lm_row(w->N, K4, X + 3 * (size_t)i, uv + 2 * (size_t)i, rows + (size_t)i * OPP_LM_ROW);
+      OPP_BARRIER();
+      if (tid == 0) {
+        w->cost_new = opp_lm_sum(rows, n, 27);
+        opp_lm_accept(w);
+      }
+      OPP_BARRIER();
+      if (w->acc)
+        for (int e = tid; e < 27; e += nt) opp_lm_store(w, e, opp_lm_sum(rows, n, e));
+    } else if (tid == 0) {   // a singular damped system: more damping
+      w->cost_new = w->cost;
+      w->pred = 0.0;
+      opp_lm_accept(w);
+    }
+    OPP_BARRIER();
+  }
+  OPP_BARRIER();
+}

@@ -9,10 +9,12 @@
         (src/inference/inference_OnePosePlus.py:11, demo.py:17)
   * `from src.models.OnePosePlus import OnePosePlus_model`
         (src/lightning_model/OnePosePlus_lightning_model.py:8 via src/models/OnePosePlus/__init__.py:1)
-and, with `pnp=True` (or `pnp="epnp"`), routes `src.utils.metric_utils.ransac_PnP` (called by `compute_query_pose_errors`,
+and, with `pnp=True` (or `pnp="epnp"` / `"loransac"` / `"auto"`), routes `src.utils.metric_utils.ransac_PnP` (called by `compute_query_pose_errors`,
 metric_utils.py:262-270, i.e. by every caller of the matcher: inference worker, demo, validation step) to the
 on-device `onepose_plus_plus_amd.pose.ransac_PnP`, which keeps the reference's signature and return tuple (`pnp="epnp"`:
-with `solver="epnp"`, the reference's own minimal solver and adaptive stop; `pnp=True`: the default P3P solver); with
+with `solver="epnp"`, the reference's own minimal solver and adaptive stop; `pnp="loransac"`: LO-RANSAC with robust
+refinement, the reference's pycolmap branch; `pnp="auto"`: whichever of the two the caller's `use_pycolmap_ransac` selects, as
+the reference would; `pnp=True`: the default P3P solver); with
 `loss=True` the training step's `Loss` (src/lightning_model/losses.py) and `fine_supervision`
 (src/models/OnePosePlus/utils/fine_supervision.py) resolve to `onepose_plus_plus_amd.losses`.
 
@@ -67,7 +69,8 @@ def _patch_attr(path, name, obj, done):
 
 
 def install(pnp=True, loss=True):
-    """-> dict of what was patched (for logging / tests).  pnp: True (P3P solver), "epnp" (the reference's EPnP) or False"""
+    """-> dict of what was patched (for logging / tests).  pnp: True (P3P solver), "epnp" (the reference's EPnP), "loransac" (its
+    pycolmap branch), "auto" (the one of the two that the caller's `use_pycolmap_ransac` selects) or False"""
     done = {}
     for path in _MODEL_PATHS:
         mod = sys.modules.get(path)
@@ -85,17 +88,17 @@ def install(pnp=True, loss=True):
         done[path] = "OnePosePlus_model"
     # keep the sub-module reachable as an attribute of the package (import machinery convention)
     setattr(sys.modules["src.models.OnePosePlus"], "OnePosePlusModel", sys.modules["src.models.OnePosePlus.OnePosePlusModel"])
-    if pnp not in (False, None, True, "epnp"):
-        raise ValueError("pnp must be True, False or 'epnp', got %r" % (pnp,))
+    if pnp not in (False, None, True, "epnp", "loransac", "auto"):
+        raise ValueError("pnp must be True, False, 'epnp', 'loransac' or 'auto', got %r" % (pnp,))
     if pnp:
         from .pose import ransac_PnP
-        if pnp == "epnp":
+        if isinstance(pnp, str):
             import functools
-            ransac_PnP = functools.partial(ransac_PnP, solver="epnp")
+            ransac_PnP = functools.partial(ransac_PnP, solver=pnp)
         try:
             mu = importlib.import_module("src.utils.metric_utils")
             mu.ransac_PnP = ransac_PnP
-            done["src.utils.metric_utils"] = "ransac_PnP (epnp)" if pnp == "epnp" else "ransac_PnP"
+            done["src.utils.metric_utils"] = "ransac_PnP (%s)" % pnp if isinstance(pnp, str) else "ransac_PnP"
         except Exception as e:      # the reference (or one of its dependencies) is not importable here
             done["src.utils.metric_utils"] = "not patched: %s" % (e,)
     if loss:

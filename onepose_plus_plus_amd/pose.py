@@ -5,7 +5,7 @@ Same call signature and return tuple `(pose [3,4], pose_homo [4,4], inliers, sta
 matches may be CUDA tensors (they then never leave the device until the 12-number pose is read)
 or numpy arrays.  Deterministic for a given `seed`.  No CPU fallback.
 
-Two minimal solvers (`solver=`):
+Three estimators (`solver=`):
   * "epnp": the reference's estimator, OpenCV 4.x `solvePnPRansac(flags=SOLVEPNP_EPNP)` as we read it (OpenCV's source is
     not available here, so no OpenCV fixtures: "parity unpinned"): EPnP on 5-match samples (P3P when there are exactly 4
     matches, one EPnP solve on all of them when there are exactly 5), inlier when the squared reprojection error <= thr^2,
@@ -22,11 +22,34 @@ Two minimal solvers (`solver=`):
   * "p3p" (default, unchanged): Grunert P3P on 3 matches + a 4th for disambiguation, Gauss-Newton refinement
     (`refine_iters`) on the inliers, instead of EPnP; every one of the `iterations` hypotheses is evaluated unless a
     `confidence` < 1 is given.
-Both: failure convention -- fewer than 4 matches, or no hypothesis producing a model, returns the reference's own
+"epnp" and "p3p": failure convention -- fewer than 4 matches, or no hypothesis producing a model, returns the reference's own
 `cv2.error` branch (identity pose, empty inliers, state False, metric_utils.py:197-204); with "p3p", when no hypothesis
 gathers 4 inliers the best one is returned with state True and whatever inliers it has; with "epnp", when none gathers 5
 the best valid hypothesis's pose is returned with state True and empty inliers (the reference's `inliers is None` branch).
-The pycolmap branch (`use_pycolmap_ransac=True`) is not reproduced: the argument is accepted and ignored.
+  * "loransac": the reference's pycolmap branch (`use_pycolmap_ransac=True`: pycolmap.absolute_pose_estimation, i.e. COLMAP 3.8
+    EstimateAbsolutePose = LORANSAC<P3PEstimator, EPNPEstimator> + RefineAbsolutePose, with pycolmap's defaults) as we read it
+    (pycolmap is not available here, so no pycolmap fixtures: "parity unpinned"; csrc/pnp_lo.hip).  As the reference's branch does:
+    a SIMPLE_PINHOLE camera [K[0,0], cx, cy] (fx serves both axes), `scale` NOT applied, `img_hw` unused.  Trial t draws 3 matches,
+    P3P gives 0..4 models and every one is scored (no 4th disambiguation match): residual = squared reprojection error, a point at
+    depth <= 0 is never an inlier, inlier when residual <= thr^2, support = (inliers, sum of their residuals), better = more
+    inliers, or as many and a smaller sum.  A model that beats the best support with more than 4 inliers is locally optimised: EPnP
+    on the best model's inliers, kept when better, repeated while the inlier count grows, at most 10 times.  After every new best
+    dyn = ceil(3 log(1 - confidence) / log(1 - r^3)), r = inliers / n (r = 1: 0; log(1 - r^3) = 0: the cap); the loop ends at the
+    first trial t >= dyn and >= min_trials (`confidence` 0.9999, `min_trials` 1000, `iterations` the cap).  Failure (identity pose,
+    empty inliers, state False): fewer than 3 matches, no model, a best inlier count of 0 or below `min_inlier_ratio` (0.01) * n.
+    The pose is then refined on the best model's inliers by Levenberg-Marquardt on sum log(1 + residual) (Cauchy, scale 1 px):
+    weights 1 / (1 + s), a step accepted only when the robust cost decreases (by at least 1e-3 of the decrease the linearised
+    model predicts, Ceres' min_relative_decrease), damping x10 / :10, stop at |gradient|_inf <= 1
+    (COLMAP's gradient_tolerance), after 100 iterations or when the damping overflows.  The inliers returned are the RANSAC
+    inliers of the best model before the refinement, as pycolmap returns them.  Where it may differ from COLMAP:
+      - samples come from the hash of (seed, trial), not COLMAP's RandomSampler; all trials run in parallel and the result is that
+        of the sequential loop over trials 0, 1, ... (see `stop` of `ransac_PnP_ex`);
+      - the cap on the trials is `iterations` (default 10000; COLMAP's max_num_trials is 100000); confidence >= 1 runs them all;
+      - P3P is Grunert's (COLMAP: Kneip-style P3P), EPnP is the one of "epnp" above (COLMAP's own EPnP port);
+      - the refinement is a plain Levenberg-Marquardt on the 6-vector pose update (damping scaled by the diagonal, a fixed factor),
+        not Ceres' trust-region strategy with its step-quality ratio, function / parameter tolerances and inner iterations; the
+        robust loss enters by its first derivative only (no second-order Triggs correction); the focal length is not refined;
+      - a depth below 1e-12 counts as "behind the camera".
 """
 import ctypes
 
@@ -45,14 +68,82 @@ def _dev_f32(a, device):
 
 
 _SOLVERS = {"p3p": 0, "epnp": 1}
+_SOLVER_NAMES = ("p3p", "epnp", "loransac")
+
+
+def _bad_solver(solver, allowed):
+    return ValueError("solver must be one of %s, got %r" % (", ".join(repr(a) for a in allowed), solver))
+
+
+def _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, confidence, min_trials, min_inlier_ratio,
+              simple_pinhole, record):
+    """`opp_pnp_loransac` -> the dict of `ransac_PnP_ex`"""
+    lib = _lib.load()
+    if device is None:
+        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
+    Kn = Kn.astype(np.float64)
+    K4 = (ctypes.c_double * 4)(Kn[0, 0], Kn[0, 0] if simple_pinhole else Kn[1, 1], Kn[0, 2], Kn[1, 2])
+    p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
+    p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
+    n = int(p2.shape[0])
+    iterations = int(iterations)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        out = torch.empty(12, dtype=torch.float64, device=device)
+        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        cnt = torch.zeros(5, dtype=torch.int32, device=device)          # n_inliers, ok, stop, n_cand, lm_iters
+        rec, bufs = None, {}
+        if record:
+            i32, f64 = torch.int32, torch.float64
+            bufs = {"samples": torch.full((iterations, 3), -1, dtype=i32, device=device),
+                    "counts": torch.full((iterations, 4), -1, dtype=i32, device=device),
+                    "sums": torch.zeros((iterations, 4), dtype=f64, device=device),
+                    "models": torch.zeros((iterations, 4, 12), dtype=f64, device=device),
+                    "cand_idx": torch.full((iterations * 4,), -1, dtype=i32, device=device),
+                    "cand_cnt": torch.full((iterations * 4,), -1, dtype=i32, device=device),
+                    "cand_sum": torch.zeros((iterations * 4,), dtype=f64, device=device),
+                    "cand_taken": torch.zeros((iterations * 4,), dtype=i32, device=device),
+                    "ransac_pose": torch.zeros(12, dtype=f64, device=device)}
+            rec = _lib.OppLoRecord(n_cand=cnt.data_ptr() + 12, lm_iters=cnt.data_ptr() + 16, **{k: v.data_ptr() for k, v in bufs.items()})
+        nbytes = lib.opp_pnp_loransac_workspace_bytes(iterations, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.opp_pnp_loransac(p2.data_ptr(), p3.data_ptr(), n, K4, float(pnp_reprojection_error), iterations,
+                                        int(seed) & 0xFFFFFFFF, float(confidence), int(min_trials), float(min_inlier_ratio),
+                                        out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4, cnt.data_ptr() + 8,
+                                        ctypes.addressof(rec) if rec is not None else None, ws.data_ptr(), nbytes, stream),
+                   "opp_pnp_loransac")
+        host = torch.cat([out, cnt.double()]).cpu().numpy()              # one D2H copy
+        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0), "stop": int(host[14])}
+        res["inliers"] = torch.nonzero(mask[:n]).to(torch.int32).cpu().numpy().reshape(-1) if res["state"] else \
+            np.zeros(0, np.int32)
+        if record:
+            nc = int(host[15])
+            res["lm_iters"] = int(host[16])
+            for k in ("samples", "counts", "sums", "models"):
+                res[k] = bufs[k].cpu().numpy()
+            for k in ("cand_idx", "cand_cnt", "cand_sum", "cand_taken"):
+                res[k] = bufs[k][:nc].cpu().numpy()
+            res["ransac_pose"] = bufs["ransac_pose"].cpu().numpy().reshape(3, 4)
+    return res
 
 
 def ransac_PnP_ex(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, iterations=10000, refine_iters=8, seed=0, device=None,
-                  solver="p3p", confidence=None, record=False):
+                  solver="p3p", confidence=None, record=False, min_trials=1000, min_inlier_ratio=0.01, simple_pinhole=True):
     """`opp_pnp_ransac_ex` -> dict(pose [3,4], inliers [k] int, state, stop, and with `record` the per-hypothesis
-    `samples` [iterations, 5] and `scores` [iterations]).  confidence None: 0.99 for "epnp", off for "p3p"."""
-    if solver not in _SOLVERS:
-        raise ValueError("solver must be 'p3p' or 'epnp', got %r" % (solver,))
+    `samples` [iterations, 5] and `scores` [iterations]).  confidence None: 0.99 for "epnp", off for "p3p", 0.9999 for "loransac".
+    solver "loransac" (`opp_pnp_loransac`; `scale` and `refine_iters` unused, `min_trials` / `min_inlier_ratio` / `simple_pinhole`
+    for it alone: simple_pinhole False uses fx and fy instead of fx for both axes): `stop` = trials the sequential loop runs, and
+    with `record`: `samples` [iterations, 3], per-model `counts` / `sums` [iterations, 4] (-1: no model, or a trial past the bound
+    that was never scored) and `models` [iterations, 4, 12] (R row-major | t), the candidate list `cand_idx` (4 * trial + model of
+    every model that beats all earlier ones), its supports after local optimisation `cand_cnt` / `cand_sum`, `cand_taken` (the
+    candidates that became the best in the sequential loop; the last one is the result), `ransac_pose` [3,4] before the
+    refinement and `lm_iters`."""
+    if solver not in _SOLVER_NAMES:
+        raise _bad_solver(solver, _SOLVER_NAMES)
+    if solver == "loransac":
+        return _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, 0.9999 if confidence is None else confidence,
+                         min_trials, min_inlier_ratio, simple_pinhole, record)
     if confidence is None:
         confidence = 0.99 if solver == "epnp" else 1.0
     lib = _lib.load()
@@ -91,15 +182,20 @@ def ransac_PnP_ex(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, iteratio
 
 
 def ransac_PnP(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, img_hw=None, use_pycolmap_ransac=False,
-               iterations=10000, refine_iters=8, seed=0, device=None, solver="p3p", confidence=None):
-    """K [3,3]; pts_2d [M,2] pixels; pts_3d [M,3].  `img_hw` / `use_pycolmap_ransac` are accepted for
-    signature compatibility (the pycolmap branch of the reference is not reproduced).  solver: "p3p" (default) or "epnp"
-    (the reference's); confidence: None = the solver's default (off for "p3p", 0.99 for "epnp"); refine_iters: "p3p" only."""
-    if solver not in _SOLVERS:
-        raise ValueError("solver must be 'p3p' or 'epnp', got %r" % (solver,))
+               iterations=10000, refine_iters=8, seed=0, device=None, solver="p3p", confidence=None, min_trials=1000,
+               min_inlier_ratio=0.01):
+    """K [3,3]; pts_2d [M,2] pixels; pts_3d [M,3].  solver: "p3p" (default), "epnp" (the reference's OpenCV branch), "loransac"
+    (the reference's pycolmap branch) or "auto" = what the reference would run: "loransac" when `use_pycolmap_ransac` is true,
+    "epnp" otherwise.  With "p3p" / "epnp" `use_pycolmap_ransac` is ignored; `img_hw` is accepted and unused, as in the reference.
+    confidence: None = the solver's default (off for "p3p", 0.99 for "epnp", 0.9999 for "loransac"); refine_iters: "p3p" only;
+    min_trials / min_inlier_ratio: "loransac" only, which also leaves `scale` unapplied (the reference's pycolmap branch does)."""
+    if solver == "auto":
+        solver = "loransac" if use_pycolmap_ransac else "epnp"
+    elif solver not in _SOLVER_NAMES:
+        raise _bad_solver(solver, _SOLVER_NAMES + ("auto",))
     if solver != "p3p" or confidence is not None:
         r = ransac_PnP_ex(K, pts_2d, pts_3d, scale, pnp_reprojection_error, iterations, refine_iters, seed, device, solver,
-                          confidence)
+                          confidence, min_trials=min_trials, min_inlier_ratio=min_inlier_ratio)
         if not r["state"]:
             return np.eye(4)[:3], np.eye(4), np.array([]).astype(bool), False
         pose = r["pose"]

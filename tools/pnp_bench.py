@@ -1,7 +1,8 @@
 """Pose-step device time per solver: opp_pnp_ransac_ex (csrc/pnp.hip) on synthetic scenes at n = 300 / 1000 / 3000 matches and
 0 / 50 / 70 % outliers, 10000 hypotheses, adaptive stop on (confidence 0.99) and off.  Times with HIP events around the launches
 (inputs already on the device), median of --reps after one warm-up.
-    python tools/pnp_bench.py [--reps 5]"""
+    python tools/pnp_bench.py [--reps 5]
+    python tools/pnp_bench.py --loransac     # opp_pnp_loransac (csrc/pnp_lo.hip) beside solver "epnp": n = 300 / 1500, 50 % outliers"""
 import argparse
 import ctypes
 import os
@@ -31,12 +32,60 @@ def scene(rng, n, outl):
     return K4, uv, X
 
 
+def _time(call, reps):
+    times = []
+    for r in range(reps + 1):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        if r:
+            times.append(e0.elapsed_time(e1))
+    return float(np.median(times))
+
+
+def loransac_rows(lib, a):
+    """the same call with the two estimators of the reference, each with its own defaults (epnp: confidence 0.99; loransac:
+    confidence 0.9999, min_trials 1000, SIMPLE_PINHOLE, no scale)"""
+    rng = np.random.default_rng(0)
+    s = torch.cuda.current_stream().cuda_stream
+    print("| n | outliers | solver | stop index | inliers | device ms |")
+    print("|---|---|---|---|---|---|")
+    for n in (300, 1500):
+        K4n, uv, X = scene(rng, n, 0.5)
+        p2 = torch.from_numpy(uv).float().cuda().contiguous()
+        p3 = torch.from_numpy(X).float().cuda().contiguous()
+        out = torch.empty(12, dtype=torch.float64, device="cuda")
+        mask = torch.empty(n, dtype=torch.int32, device="cuda")
+        cnt = torch.zeros(3, dtype=torch.int32, device="cuda")
+        K4 = (ctypes.c_double * 4)(*K4n)
+        nb = lib.opp_pnp_ex_workspace_bytes(a.iterations, n)
+        ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+        ms = _time(lambda: _lib.check(lib.opp_pnp_ransac_ex(p2.data_ptr(), p3.data_ptr(), n, K4, 3.3, 1000.0, a.iterations, 1, 8, 1, 0.99,
+                                                            out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4,
+                                                            cnt.data_ptr() + 8, None, None, ws.data_ptr(), nb, s), "pnp_ex"), a.reps)
+        c = cnt.cpu().numpy()
+        print("| %d | 50 %% | epnp | %d | %d | %.3f |" % (n, c[2], c[0], ms), flush=True)
+        K4 = (ctypes.c_double * 4)(K4n[0], K4n[0], K4n[2], K4n[3])
+        nb = lib.opp_pnp_loransac_workspace_bytes(a.iterations, n)
+        ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+        ms = _time(lambda: _lib.check(lib.opp_pnp_loransac(p2.data_ptr(), p3.data_ptr(), n, K4, 3.3, a.iterations, 1, 0.9999, 1000, 0.01,
+                                                           out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4,
+                                                           cnt.data_ptr() + 8, None, ws.data_ptr(), nb, s), "pnp_loransac"), a.reps)
+        c = cnt.cpu().numpy()
+        print("| %d | 50 %% | loransac | %d | %d | %.3f |" % (n, c[2], c[0], ms), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iterations", type=int, default=10000)
+    ap.add_argument("--loransac", action="store_true")
     a = ap.parse_args()
     lib = _lib.load()
+    if a.loransac:
+        return loransac_rows(lib, a)
     rng = np.random.default_rng(0)
     s = torch.cuda.current_stream().cuda_stream
     print("| n | outliers | solver | confidence | stop index | inliers | device ms |")
