@@ -581,6 +581,24 @@ int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_points, const
                      double min_inlier_ratio, double* pose_out, int* inlier_mask, int* n_inliers, int* ok,
                      int* stop_out, const OppLoRecord* record, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- pose-error metrics (the scoring half of compute_query_pose_errors, src/utils/metric_utils.py:207-292) --------
+ * Scores n_poses poses of ONE model in a single enqueue (at most three launches, no host synchronisation, no allocation):
+ * query_pose_error (:91-118), add_metric's mean distance (:55-87; ADD, or ADD-S = for every TARGET point the nearest PREDICTED
+ * point, as cKDTree(model_pred).query(model_target) does) and projection_2d_error (:31-53; divides by z, no guard).  All fp64.
+ * Device pointers: model_pts [n_points][3] fp32 (NULL with n_points = 0: only the 3x3 / translation metrics); pose_pred, pose_gt
+ * [n_poses][12] row-major 3x4 R | t; K [n_poses][9] row-major, or NULL = no 2D error; syn [n_poses] 0 = ADD, 1 = ADD-S, or NULL =
+ * all 0 (the ADD-S sweep is then not launched); valid [n_poses] 0 = failed pose, or NULL = all valid.  t_to_cm: 100 for models in
+ * 'm', 1 for 'cm', 0.1 for 'mm'.  out [n_poses][4] = rotation error (degrees; trace clamped from above only, as upstream),
+ * translation error (cm), mean distance (model units), mean 2D error (pixels; NaN without K, both NaN without points); a row with
+ * valid = 0 is +inf four times.  Results are bit-identical from run to run (fixed-order sums, no atomics).  A workspace smaller
+ * than opp_pose_metrics_workspace_bytes(n_poses, n_points) is refused before any launch; the size includes the ADD-S minima
+ * (n_poses * ceil(n_points / 1024) * n_points doubles, about 25 MB at 20000 points and 8 poses) whether or not `syn` is given.
+ * In the ADD-S sweep a NaN distance (a non-finite pose) is skipped, where numpy's min would propagate it. */
+size_t opp_pose_metrics_workspace_bytes(int n_poses, int n_points);
+int opp_pose_metrics(const float* model_pts, int n_points, const double* pose_pred, const double* pose_gt, const double* K,
+                     const unsigned char* syn, const unsigned char* valid, int n_poses, double t_to_cm, double* out,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* Tuning aid (libraries built with -DOPP_TUNING only; otherwise returns an error): device buffer (4 x uint64 per
  * wave) for the phase time stamps written by the timed conv variants (tile_cfg 120 = 256x128 / 8 waves,
  * 121 = 128x128 / 4 waves, 122 = 128x128 / 8 waves); NULL disables. */

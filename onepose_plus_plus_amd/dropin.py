@@ -14,7 +14,8 @@ metric_utils.py:262-270, i.e. by every caller of the matcher: inference worker, 
 on-device `onepose_plus_plus_amd.pose.ransac_PnP`, which keeps the reference's signature and return tuple (`pnp="epnp"`:
 with `solver="epnp"`, the reference's own minimal solver and adaptive stop; `pnp="loransac"`: LO-RANSAC with robust
 refinement, the reference's pycolmap branch; `pnp="auto"`: whichever of the two the caller's `use_pycolmap_ransac` selects, as
-the reference would; `pnp=True`: the default P3P solver); with
+the reference would; `pnp=True`: the default P3P solver); with `metrics=True` (off by default) `compute_query_pose_errors` itself is replaced
+by a wrapper around `onepose_plus_plus_amd.metrics.compute_query_pose_errors`, which scores the poses on the device; with
 `loss=True` the training step's `Loss` (src/lightning_model/losses.py) and `fine_supervision`
 (src/models/OnePosePlus/utils/fine_supervision.py) resolve to `onepose_plus_plus_amd.losses`.
 
@@ -29,6 +30,7 @@ import types
 from .model import OnePosePlus_model
 
 _MODEL_PATHS = ("src.models.OnePosePlus.OnePosePlusModel", "src.models.OnePosePlus")
+_METRICS_CALLERS = ("src.inference.inference_OnePosePlus_worker", "src.lightning_model.OnePosePlus_lightning_model")
 
 
 def _real_dirs(name):
@@ -68,9 +70,48 @@ def _patch_attr(path, name, obj, done):
     done[path] = name
 
 
-def install(pnp=True, loss=True):
+def _metrics_wrapper(pnp):
+    """`compute_query_pose_errors(data, configs, training=False)` for the reference's callers: the model and its diameter are loaded
+    as metric_utils.py:236-252 does (the reference's own `load_points_from_cad` / `model_diameter_from_bbox`), the poses come
+    from `pose.ransac_PnP` (the solver `install(pnp=...)` names) -- with `pnp=False` from whatever `metric_utils.ransac_PnP` is when
+    the call is made, i.e. the reference's OpenCV / pycolmap function -- and are scored on the device by `metrics.pose_metrics`"""
+    import os.path as osp
+
+    import numpy as np
+
+    from . import metrics
+    pnp_kwargs = {"solver": pnp} if isinstance(pnp, str) else {}
+    if not pnp:
+        def reference_pnp(*args, **kwargs):
+            return sys.modules["src.utils.metric_utils"].ransac_PnP(*args, **kwargs)
+        pnp_kwargs = {"ransac_PnP": reference_pnp}
+
+    def compute_query_pose_errors(data, configs, training=False):
+        model_vertices = diameter = None
+        if "eval_ADD_metric" in configs and configs["eval_ADD_metric"] and not training:
+            from src.utils.sample_points_on_cad import load_points_from_cad, model_diameter_from_bbox
+            image_path = data["query_image_path"]
+            root = image_path.rsplit("/", 3)[0]
+            model_path = osp.join(root, "model_eval.ply")
+            if not osp.exists(model_path):
+                model_path = osp.join(root, "model.ply")
+            diameter_file_path = osp.join(root, "diameter.txt")
+            if osp.exists(model_path):       # upstream logs an error and evaluates no ADD otherwise
+                model_vertices, bbox = load_points_from_cad(model_path)   # N*3
+                diameter = np.loadtxt(diameter_file_path) if osp.exists(diameter_file_path) else model_diameter_from_bbox(bbox)
+        return metrics.compute_query_pose_errors(data, configs, training=training, model_vertices=model_vertices, diameter=diameter,
+                                                 **pnp_kwargs)
+
+    return compute_query_pose_errors
+
+
+def install(pnp=True, loss=True, metrics=False):
     """-> dict of what was patched (for logging / tests).  pnp: True (P3P solver), "epnp" (the reference's EPnP), "loransac" (its
-    pycolmap branch), "auto" (the one of the two that the caller's `use_pycolmap_ransac` selects) or False"""
+    pycolmap branch), "auto" (the one of the two that the caller's `use_pycolmap_ransac` selects) or False.  metrics: True also
+    replaces `src.utils.metric_utils.compute_query_pose_errors` by the on-device scoring of `onepose_plus_plus_amd.metrics`
+    (recorded under "src.utils.metric_utils:compute_query_pose_errors") and rebinds the name in the reference's two callers when
+    they were imported already (recorded under "<module>:compute_query_pose_errors"); off by default.  With `pnp=False` the
+    wrapper scores the poses of the reference's own `ransac_PnP` (OpenCV / pycolmap) on the device"""
     done = {}
     for path in _MODEL_PATHS:
         mod = sys.modules.get(path)
@@ -101,6 +142,22 @@ def install(pnp=True, loss=True):
             done["src.utils.metric_utils"] = "ransac_PnP (%s)" % pnp if isinstance(pnp, str) else "ransac_PnP"
         except Exception as e:      # the reference (or one of its dependencies) is not importable here
             done["src.utils.metric_utils"] = "not patched: %s" % (e,)
+    if metrics:
+        key = "src.utils.metric_utils:compute_query_pose_errors"
+        try:
+            mu = importlib.import_module("src.utils.metric_utils")
+            mu.compute_query_pose_errors = _metrics_wrapper(pnp)
+            wrapper = mu.compute_query_pose_errors
+            done[key] = "compute_query_pose_errors (%s)" % pnp if isinstance(pnp, str) else "compute_query_pose_errors"
+            # the reference's callers bind the name when they are imported (inference_OnePosePlus_worker.py:4,
+            # OnePosePlus_lightning_model.py:15): one imported before install() is rebound as well
+            for path in _METRICS_CALLERS:
+                caller = sys.modules.get(path)
+                if caller is not None and hasattr(caller, "compute_query_pose_errors"):
+                    caller.compute_query_pose_errors = wrapper
+                    done[path + ":compute_query_pose_errors"] = done[key]
+        except Exception as e:      # the reference (or one of its dependencies) is not importable here
+            done[key] = "not patched: %s" % (e,)
     if loss:
         # training step (src/lightning_model/OnePosePlus_lightning_model.py:9,14): `fine_supervision(batch, hparams)` and
         # `Loss(hparams["loss"])` -> the module's own (the focal loss over the B x N x L matrix runs in libopp_hip.so)
