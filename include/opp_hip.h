@@ -527,7 +527,9 @@ int opp_segmented_mean(const float* rows, int D, const long long* offsets, int n
  * pts3d [n][3] fp32 on the device; K4 = {fx, fy, cx, cy} on the HOST; `scale` multiplies the 3D
  * points before solving and divides the translation after (reference `point_cloud_rescale`).
  * Outputs on the device: pose_out [12] doubles = row-major [R | t] (3x4), inlier_mask [n] (0/1),
- * n_inliers, ok (0 -> identity pose, the reference's cv2.error branch).  Deterministic for a seed. */
+ * n_inliers, ok (0 -> identity pose, the reference's cv2.error branch).  Deterministic for a seed.
+ * Fewer than 4 matches give that failure result; with n_points == 0 pts2d and pts3d may be NULL (an
+ * empty tensor has no address) and inlier_mask is not written, as in opp_pnp_ransac_ex. */
 size_t opp_pnp_workspace_bytes(int iterations);
 int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_points, const double* K4,
                    double reproj_error_px, double scale, int iterations, unsigned seed,
@@ -547,6 +549,25 @@ int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, cons
                       int refine_iters, int solver, double confidence, double* pose_out, int* inlier_mask,
                       int* n_inliers, int* ok, int* stop_out, int* samples_out, int* scores_out,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* opp_pnp_ransac_ex for a whole batch in one enqueue, with no device-to-host copy and no host decision on a sample's size.
+ * The matches of the n_samples (1..1024) samples lie concatenated in sample order: pts2d [n_total][2], pts3d [n_total][3];
+ * offsets [n_samples + 1] (device) delimits them, so sample b has offsets[b+1] - offsets[b] matches, a number the host need
+ * not know (a pair of offsets that is no segment of [0, n_total] makes an empty sample).  K4 [n_samples][4] and seeds
+ * [n_samples] are DEVICE arrays; the threshold, scale, iterations, solver and confidence hold for every sample.  Outputs on
+ * the device: pose_out [n_samples][12], inlier_mask [n_total] (0/1, indexed like the matches), n_inliers, ok and stop
+ * [n_samples].  Sample b's outputs are bit for bit those of opp_pnp_ransac_ex on its slice with K4[b] and seeds[b]; a failed
+ * sample (fewer than 4 matches, no model) gets the identity pose, a zeroed mask segment, ok = 0, n_inliers = 0.  n_total = 0
+ * is legal (every sample fails).
+ * opp_pnp_offsets makes `offsets` from the matcher's batch ids m_bids [n_total] (int64, non-decreasing, in [0, n_samples),
+ * as the coarse matcher's ordered compaction emits them) by a lower-bound search per boundary; *bad (device) becomes 1 when
+ * the ids break that contract and 0 otherwise. */
+size_t opp_pnp_batch_workspace_bytes(int iterations, int n_samples, int n_total);
+int opp_pnp_offsets(const long long* m_bids, int n_total, int n_samples, int* offsets, int* bad, void* stream);
+int opp_pnp_ransac_batch(const float* pts2d, const float* pts3d, const int* offsets, int n_samples, int n_total,
+                         const double* K4, const unsigned* seeds, double reproj_error_px, double scale, int iterations,
+                         int refine_iters, int solver, double confidence, double* pose_out, int* inlier_mask,
+                         int* n_inliers, int* ok, int* stop, void* workspace, size_t workspace_bytes, void* stream);
 
 /* LO-RANSAC with robust refinement: the reference's pycolmap branch (pycolmap.absolute_pose_estimation, i.e. COLMAP 3.8
  * EstimateAbsolutePose: LORANSAC<P3PEstimator, EPNPEstimator>, then RefineAbsolutePose under a Cauchy loss).  Trial t draws 3

@@ -159,6 +159,11 @@ SIGNATURES = {
     "opp_pnp_ransac_ex": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,
                                   c_int, ctypes.c_uint, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "opp_pnp_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "opp_pnp_offsets": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "opp_pnp_ransac_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_double,
+                                     ctypes.c_double, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_pnp_loransac_workspace_bytes": (c_size_t, [c_int, c_int]),
     "opp_pnp_loransac": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, c_int, ctypes.c_uint,
                                  ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -3,14 +3,16 @@
 
 `pose_metrics` scores a batch of poses of one model in one enqueue and one device-to-host copy: rotation error (degrees),
 translation error (cm), ADD or ADD-S mean distance, mean 2D projection error.  `query_pose_error`, `projection_2d_error` and
-`add_metric` keep the reference's signatures and return types (each is a batch of one); `compute_query_pose_errors` runs
-`pose.ransac_PnP` per sample and scores the whole batch in one call; `aggregate_metrics` is the dataset-level summary.  All
+`add_metric` keep the reference's signatures and return types (each is a batch of one); `compute_query_pose_errors` estimates
+the batch's poses (`pose.ransac_PnP_batch`, or `pose.ransac_PnP` per sample) and scores the whole batch in one call; `aggregate_metrics` is the dataset-level summary.  All
 arithmetic is float64, as the reference's numpy is (float32 vertices times float64 poses promote to float64).  No CPU fallback.
 
 Formulas as written upstream: the trace of Rp Rg^T is clamped from above only (:116), so a rotation error next to 180 degrees
 may come out NaN there and here alike; ADD-S takes for every TARGET point the nearest PREDICTED point (:79-81); the projection
 divides by z without a guard (:41).
 """
+import warnings
+
 import numpy as np
 import torch
 
@@ -116,12 +118,36 @@ def _np(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
+def _batch_poses(data, configs, query_K, pnp_kwargs):
+    """The poses of the whole batch from ONE `pose.ransac_PnP_batch` call on data['m_bids'], or None where the per-sample loop
+    has to run: the solver is "loransac" (named, or what "auto" resolves to), which has no batch pass, or the ids are not in the
+    matcher's order (non-decreasing, in [0, B)), which the loop's `m_bids == bs` selection does not need.  The order is checked
+    on the device and read back with the poses, so such ids pay for the batch pass AND the loop; a RuntimeWarning says so."""
+    from . import pose
+    solver = pnp_kwargs.get("solver", "p3p")
+    if solver == "auto":
+        solver = "loransac" if configs["use_pycolmap_ransac"] else "epnp"
+    if solver not in ("p3p", "epnp") or query_K.shape[0] > 1024:   # 1024: the batch pass's limit on B
+        return None
+    kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "min_trials", "min_inlier_ratio")}   # the last two: "loransac" only
+    try:
+        return pose.ransac_PnP_batch(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
+                                     scale=configs["point_cloud_rescale"],
+                                     pnp_reprojection_error=configs["pnp_reprojection_error"], solver=solver, **kw)
+    except pose.BatchIdsError:
+        warnings.warn("compute_query_pose_errors: m_bids is not non-decreasing in [0, B); the batch pass was discarded and the "
+                      "poses are estimated per sample", RuntimeWarning, stacklevel=3)
+        return None
+
+
 @torch.no_grad()
 def compute_query_pose_errors(data, configs, training=False, model_vertices=None, diameter=None, syn=None, **pnp_kwargs):
     """Mirror of metric_utils.py:207-292: reads m_bids, mkpts_3d_db, mkpts_query_f, q_hw_i, query_image_scale, query_intrinsic,
-    query_pose_gt (and query_intrinsic_origin, query_image_path for ADD) from `data`, runs `pose.ransac_PnP` per sample with
-    configs' point_cloud_rescale / pnp_reprojection_error / use_pycolmap_ransac (`pnp_kwargs`, e.g. solver=, are passed through;
-    `ransac_PnP=` names another estimator with the reference's signature and return tuple, which gets numpy matches),
+    query_pose_gt (and query_intrinsic_origin, query_image_path for ADD) from `data`, estimates the poses with
+    configs' point_cloud_rescale / pnp_reprojection_error / use_pycolmap_ransac (`pnp_kwargs`, e.g. solver=, are passed through):
+    ONE `pose.ransac_PnP_batch` call for the solvers "p3p" and "epnp", `pose.ransac_PnP` per sample for "loransac", for ids that
+    are not in the matcher's order and for `ransac_PnP=`, which names another estimator with the reference's signature and
+    return tuple and gets numpy matches (the batch call and the loop give the same bytes),
     scores the whole batch in ONE `pose_metrics` call and writes R_errs, t_errs, inliers, the empty *_c lists and pose_pred
     [B,4,4]; ADD and proj2D when configs['eval_ADD_metric'] is set, the call is not training and `model_vertices` (with
     `diameter`) is given -- the reference loads both from the object's directory, `dropin.install(metrics=True)` does the same.
@@ -156,19 +182,25 @@ def compute_query_pose_errors(data, configs, training=False, model_vertices=None
         query_K_origin = _np(data["query_intrinsic_origin"]).astype(np.float64)
         data.update({"ADD": [], "proj2D": []})
 
-    pose_pred, inliers, valid = [], [], []
-    for bs in range(B):
-        mask = m_bids == bs
-        pts_2d, pts_3d = mkpts_query[mask], mkpts_3d[mask]
-        if host_matches:
-            pts_2d, pts_3d = _np(pts_2d), _np(pts_3d)
-        _, pose_homo, inl, state = ransac_PnP(query_K[bs], pts_2d, pts_3d, scale=configs["point_cloud_rescale"],
-                                              img_hw=img_orig_size[bs].tolist(),
-                                              pnp_reprojection_error=configs["pnp_reprojection_error"],
-                                              use_pycolmap_ransac=configs["use_pycolmap_ransac"], **pnp_kwargs)
-        pose_pred.append(pose_homo if state else np.eye(4))
-        inliers.append(inl if state else np.array([]).astype(bool))
-        valid.append(bool(state))
+    batch = None if host_matches or not B else _batch_poses(data, configs, query_K, pnp_kwargs)
+    if batch is not None:
+        valid = [bool(s) for s in batch["state"]]
+        pose_pred = [batch["pose_homo"][bs] if valid[bs] else np.eye(4) for bs in range(B)]
+        inliers = list(batch["inliers"])
+    else:
+        pose_pred, inliers, valid = [], [], []
+        for bs in range(B):
+            mask = m_bids == bs
+            pts_2d, pts_3d = mkpts_query[mask], mkpts_3d[mask]
+            if host_matches:
+                pts_2d, pts_3d = _np(pts_2d), _np(pts_3d)
+            _, pose_homo, inl, state = ransac_PnP(query_K[bs], pts_2d, pts_3d, scale=configs["point_cloud_rescale"],
+                                                  img_hw=img_orig_size[bs].tolist(),
+                                                  pnp_reprojection_error=configs["pnp_reprojection_error"],
+                                                  use_pycolmap_ransac=configs["use_pycolmap_ransac"], **pnp_kwargs)
+            pose_pred.append(pose_homo if state else np.eye(4))
+            inliers.append(inl if state else np.array([]).astype(bool))
+            valid.append(bool(state))
     pose_pred = np.stack(pose_pred) if B else np.zeros((0, 4, 4))   # [B*4*4]
     if B:
         res = pose_metrics(model_vertices if eval_add else None, pose_pred, query_pose_gt, K=query_K_origin, syn=bool(syn) if eval_add else False,

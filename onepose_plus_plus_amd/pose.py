@@ -3,7 +3,8 @@
 
 Same call signature and return tuple `(pose [3,4], pose_homo [4,4], inliers, state)`; the
 matches may be CUDA tensors (they then never leave the device until the 12-number pose is read)
-or numpy arrays.  Deterministic for a given `seed`.  No CPU fallback.
+or numpy arrays.  Deterministic for a given `seed`.  No CPU fallback.  `ransac_PnP_batch` estimates the poses of a whole batch
+in one pass (csrc/pnp_batch.hip; "p3p" and "epnp"), each sample bit-identical to its single call.
 
 Three estimators (`solver=`):
   * "epnp": the reference's estimator, OpenCV 4.x `solvePnPRansac(flags=SOLVEPNP_EPNP)` as we read it (OpenCV's source is
@@ -179,6 +180,104 @@ def ransac_PnP_ex(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, iteratio
             res["samples"] = samples.cpu().numpy()
             res["scores"] = scores.cpu().numpy()
     return res
+
+
+class BatchIdsError(ValueError):
+    """`ransac_PnP_batch`: the batch ids are not non-decreasing, or not all in [0, B)"""
+
+
+def _batch_solver(solver, use_pycolmap_ransac):
+    """the solver a batch call runs ("p3p" / "epnp"); "loransac", named or resolved from "auto", has no batch pass"""
+    if solver == "auto":
+        solver = "loransac" if use_pycolmap_ransac else "epnp"
+    elif solver not in _SOLVER_NAMES:
+        raise _bad_solver(solver, _SOLVER_NAMES + ("auto",))
+    if solver == "loransac":
+        raise NotImplementedError('ransac_PnP_batch runs "p3p" and "epnp"; LO-RANSAC is per sample: call ransac_PnP(solver="loransac") '
+                                  "or ransac_PnP_ex for each sample")
+    return solver
+
+
+def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, scale=1, pnp_reprojection_error=5,
+                     iterations=10000, refine_iters=8, seed=0, solver="p3p", confidence=None, device=None,
+                     use_pycolmap_ransac=False):
+    """`ransac_PnP_ex` for B samples in one pass (`opp_pnp_ransac_batch`, csrc/pnp_batch.hip): sample b's results are bit for bit
+    those of `ransac_PnP_ex(K[b], <its matches>, seed=seed[b], ...)`.  K [B,3,3]; pts_2d [M,2] and pts_3d [M,3] hold the matches of
+    all samples concatenated in sample order (CUDA tensors stay on the device); give exactly one of `m_bids` [M] (the matcher's
+    batch ids, non-decreasing, in [0, B)) and `offsets` [B+1] (sample b = matches offsets[b]:offsets[b+1]); seed: an int for every
+    sample, or B of them; solver "p3p", "epnp" or "auto" (with `use_pycolmap_ransac`, as in `ransac_PnP`; "loransac" raises
+    NotImplementedError); confidence None: the solver's default, as in `ransac_PnP_ex`.
+    -> dict: pose [B,3,4] and pose_homo [B,4,4] float64, state [B] bool, stop [B], inliers: B arrays [k,1] int32 of indices LOCAL to
+    the sample (an empty bool array where state is False), pose_dev: the [B,3,4] float64 CUDA tensor.  Two device-to-host copies
+    whatever B is (poses + counts + offsets, and the mask); ids that break the contract raise ValueError after the first."""
+    solver = _batch_solver(solver, use_pycolmap_ransac)
+    if (m_bids is None) == (offsets is None):
+        raise ValueError("ransac_PnP_batch: give exactly one of m_bids and offsets")
+    if confidence is None:
+        confidence = 0.99 if solver == "epnp" else 1.0
+    lib = _lib.load()
+    if device is None:
+        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
+    Kn = Kn.astype(np.float64).reshape(-1, 3, 3)
+    B = int(Kn.shape[0])
+    if batch_size is not None and int(batch_size) != B:
+        raise ValueError("ransac_PnP_batch: K holds %d matrices, batch_size is %d" % (B, int(batch_size)))
+    if not 1 <= B <= 1024:
+        raise ValueError("ransac_PnP_batch: 1 to 1024 samples, got %d" % B)
+    seeds = np.broadcast_to(np.asarray(seed, dtype=np.int64) & 0xFFFFFFFF, (B,)) if np.ndim(seed) == 0 else \
+        np.asarray(seed, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
+    if seeds.shape != (B,):
+        raise ValueError("ransac_PnP_batch: seed must be an int or %d ints" % B)
+    p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
+    p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
+    n = int(p2.shape[0])
+    if int(p3.shape[0]) != n:
+        raise ValueError("ransac_PnP_batch: %d 2D points, %d 3D points" % (n, int(p3.shape[0])))
+    iterations = int(iterations)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
+        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
+        if m_bids is not None:
+            ids = m_bids if torch.is_tensor(m_bids) else torch.from_numpy(np.ascontiguousarray(m_bids))
+            ids = ids.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+            if int(ids.shape[0]) != n:
+                raise ValueError("ransac_PnP_batch: %d batch ids for %d matches" % (int(ids.shape[0]), n))
+            off = torch.empty(B + 1, dtype=torch.int32, device=device)
+            _lib.check(lib.opp_pnp_offsets(ids.data_ptr(), n, B, off.data_ptr(), cnt.data_ptr() + 12 * B, stream), "opp_pnp_offsets")
+        else:
+            off = offsets if torch.is_tensor(offsets) else torch.from_numpy(np.ascontiguousarray(offsets))
+            off = off.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+            if int(off.shape[0]) != B + 1:
+                raise ValueError("ransac_PnP_batch: offsets needs %d entries, got %d" % (B + 1, int(off.shape[0])))
+        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
+        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        nbytes = lib.opp_pnp_batch_workspace_bytes(iterations, B, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.opp_pnp_ransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr(), B, n, K4.data_ptr(), seeds_d.data_ptr(),
+                                            float(pnp_reprojection_error), float(scale), iterations, int(refine_iters),
+                                            _SOLVERS[solver], float(confidence), out.data_ptr(), mask.data_ptr(), cnt.data_ptr(),
+                                            cnt.data_ptr() + 4 * B, cnt.data_ptr() + 8 * B, ws.data_ptr(), nbytes, stream),
+                   "opp_pnp_ransac_batch")
+        host = torch.cat([out.reshape(-1), cnt.double(), off.double()]).cpu().numpy()   # D2H copy 1 of 2
+        if host[12 * B + 3 * B] != 0:
+            raise BatchIdsError("ransac_PnP_batch: m_bids must be non-decreasing with values in [0, %d)" % B)
+        mask_h = mask[:n].cpu().numpy()                                               # D2H copy 2 of 2
+    pose = host[:12 * B].reshape(B, 3, 4).copy()
+    state = host[13 * B:14 * B] != 0
+    stop = host[14 * B:15 * B].astype(np.int64)
+    off_h = host[15 * B + 1:].astype(np.int64)
+    pose_homo = np.concatenate([pose, np.broadcast_to(np.array([[[0.0, 0.0, 0.0, 1.0]]]), (B, 1, 4))], axis=1)
+    inliers = []
+    for b in range(B):
+        lo, hi = int(off_h[b]), int(off_h[b + 1])
+        if state[b] and 0 <= lo <= hi <= n:
+            inliers.append(np.nonzero(mask_h[lo:hi])[0].astype(np.int32).reshape(-1, 1))
+        else:
+            inliers.append(np.array([]).astype(bool))
+    return {"pose": pose, "pose_homo": pose_homo, "state": state, "stop": stop, "inliers": inliers, "pose_dev": out}
 
 
 def ransac_PnP(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, img_hw=None, use_pycolmap_ransac=False,
