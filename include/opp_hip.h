@@ -514,6 +514,21 @@ int opp_layer_norm(const float* x, const float* gamma, const float* beta, const 
 int opp_image_ingest_u8(const unsigned char* src, int h, int w, int src_stride, int h_new, int w_new,
                         float* dst, int dst_stride, unsigned char* dst_u8, void* stream);
 
+/* ---- tracking crop (demo.py:98-134) --------------------------------------------------------------
+ * n_boxes crops of one 8-bit grayscale frame [h][src_stride] on the device, each crop_size x crop_size:
+ * crop_img_by_bbox (local_feature_2D_detector.py:133-159) = two cv2.warpAffine(INTER_LINEAR, constant
+ * border 0) -- the window [x0, y0, x1, y1] copied with zeros outside the frame, then scaled by
+ * crop_size / (x1 - x0) about its centre (a box that is not square is cut or zero-padded vertically) --
+ * as 8-bit fixed point, then fp32 / 255.  boxes: int32 [n_boxes][4] on the DEVICE, read by the kernel;
+ * boxes_host: the same values on the host, checked before the launch.  Refused without any launch:
+ * crop_size not a power of two in [64, 1024], an empty box (x1 - x0 < 1 or y1 - y0 < 1), a frame side
+ * or box coordinate at or beyond 32767.  No tap reads outside the frame, whatever the boxes hold.
+ * dst (fp32 [n_boxes][crop_size][crop_size]) and dst_u8 (the same crops as 8-bit values) are both
+ * optional, at least one must be given. */
+int opp_crop_warp_u8(const unsigned char* src, int h, int w, int src_stride, const int* boxes,
+                     const int* boxes_host, int n_boxes, int crop_size, float* dst, unsigned char* dst_u8,
+                     void* stream);
+
 /* ---- per-object descriptor bank (the step before the path) ----------------------
  * mean_descriptors_and_scores (src/sfm_utils/postprocess/feature_process.py:527-541): out[i][:] = mean over rows
  * [offsets[i], offsets[i+1]) of `rows` [R][D] fp32 (the 2D features of the track of 3D point i, concatenated in
