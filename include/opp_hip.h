@@ -617,6 +617,23 @@ int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_points, const
                      double min_inlier_ratio, double* pose_out, int* inlier_mask, int* n_inliers, int* ok,
                      int* stop_out, const OppLoRecord* record, void* workspace, size_t workspace_bytes, void* stream);
 
+/* opp_pnp_loransac for a whole batch in one enqueue, with no device-to-host copy and no host decision on a sample's size: the
+ * batch conventions of opp_pnp_ransac_batch (matches concatenated in sample order, `offsets` [n_samples + 1], K4 [n_samples][4]
+ * and seeds [n_samples] DEVICE arrays, a pair of offsets that is no segment of [0, n_total] makes an empty sample; offsets from
+ * opp_pnp_offsets).  The threshold, iterations, confidence, min_trials and min_inlier_ratio hold for every sample.  Outputs on
+ * the device: pose_out [n_samples][12], inlier_mask [n_total] (0/1, indexed like the matches), n_inliers, ok and stop
+ * [n_samples]; every entry is written.  Sample b's outputs are bit for bit those of opp_pnp_loransac on its slice with K4[b]
+ * and seeds[b]; a failed sample (fewer than 3 matches, no model, too few inliers) gets the identity pose, a zeroed mask segment,
+ * ok = 0, n_inliers = 0 (and stop = 0 with fewer than 3 matches).  n_total = 0 is legal (every sample fails).  A focal length
+ * <= 0 cannot be refused here (K4 is on the device): the caller checks it.  There are no record outputs.  The workspace holds
+ * about 948 * iterations bytes per sample plus 3496 bytes per match; one that is too small is refused before any launch. */
+size_t opp_pnp_loransac_batch_workspace_bytes(int iterations, int n_samples, int n_total);
+int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, const int* offsets, int n_samples, int n_total,
+                           const double* K4, const unsigned* seeds, double reproj_error_px, int iterations,
+                           double confidence, int min_trials, double min_inlier_ratio, double* pose_out,
+                           int* inlier_mask, int* n_inliers, int* ok, int* stop, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- pose-error metrics (the scoring half of compute_query_pose_errors, src/utils/metric_utils.py:207-292) --------
  * Scores n_poses poses of ONE model in a single enqueue (at most three launches, no host synchronisation, no allocation):
  * query_pose_error (:91-118), add_metric's mean distance (:55-87; ADD, or ADD-S = for every TARGET point the nearest PREDICTED

@@ -4,7 +4,7 @@
 `pose_metrics` scores a batch of poses of one model in one enqueue and one device-to-host copy: rotation error (degrees),
 translation error (cm), ADD or ADD-S mean distance, mean 2D projection error.  `query_pose_error`, `projection_2d_error` and
 `add_metric` keep the reference's signatures and return types (each is a batch of one); `compute_query_pose_errors` estimates
-the batch's poses (`pose.ransac_PnP_batch`, or `pose.ransac_PnP` per sample) and scores the whole batch in one call; `aggregate_metrics` is the dataset-level summary.  All
+the batch's poses (`pose.ransac_PnP_batch` / `pose.loransac_PnP_batch`, or `pose.ransac_PnP` per sample) and scores the whole batch in one call; `aggregate_metrics` is the dataset-level summary.  All
 arithmetic is float64, as the reference's numpy is (float32 vertices times float64 poses promote to float64).  No CPU fallback.
 
 Formulas as written upstream: the trace of Rp Rg^T is clamped from above only (:116), so a rotation error next to 180 degrees
@@ -118,19 +118,26 @@ def _np(a):
     return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
 
 
-def _batch_poses(data, configs, query_K, pnp_kwargs):
-    """The poses of the whole batch from ONE `pose.ransac_PnP_batch` call on data['m_bids'], or None where the per-sample loop
-    has to run: the solver is "loransac" (named, or what "auto" resolves to), which has no batch pass, or the ids are not in the
-    matcher's order (non-decreasing, in [0, B)), which the loop's `m_bids == bs` selection does not need.  The order is checked
-    on the device and read back with the poses, so such ids pay for the batch pass AND the loop; a RuntimeWarning says so."""
+def _batch_poses(data, configs, query_K, pnp_kwargs, batch_loransac=False):
+    """The poses of the whole batch from ONE batch call on data['m_bids'] -- `pose.ransac_PnP_batch` for "p3p" / "epnp",
+    `pose.loransac_PnP_batch` for "loransac" (named, or what "auto" resolves to) when `batch_loransac` is set -- or None where the
+    per-sample loop has to run: "loransac" without `batch_loransac`, or ids that are not in the matcher's order (non-decreasing, in
+    [0, B)), which the loop's `m_bids == bs` selection does not need.  The order is checked on the device and read back with the
+    poses, so such ids pay for the batch pass AND the loop; a RuntimeWarning says so."""
     from . import pose
     solver = pnp_kwargs.get("solver", "p3p")
     if solver == "auto":
         solver = "loransac" if configs["use_pycolmap_ransac"] else "epnp"
-    if solver not in ("p3p", "epnp") or query_K.shape[0] > 1024:   # 1024: the batch pass's limit on B
+    if solver not in ("p3p", "epnp", "loransac") or query_K.shape[0] > 1024:   # 1024: the batch passes' limit on B
         return None
-    kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "min_trials", "min_inlier_ratio")}   # the last two: "loransac" only
+    if solver == "loransac" and not batch_loransac:
+        return None
     try:
+        if solver == "loransac":   # the reference's pycolmap branch: no `scale`; `refine_iters` is "p3p"'s
+            kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "scale", "refine_iters")}
+            return pose.loransac_PnP_batch(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
+                                           pnp_reprojection_error=configs["pnp_reprojection_error"], **kw)
+        kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "min_trials", "min_inlier_ratio")}   # the last two: "loransac" only
         return pose.ransac_PnP_batch(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
                                      scale=configs["point_cloud_rescale"],
                                      pnp_reprojection_error=configs["pnp_reprojection_error"], solver=solver, **kw)
@@ -145,7 +152,8 @@ def compute_query_pose_errors(data, configs, training=False, model_vertices=None
     """Mirror of metric_utils.py:207-292: reads m_bids, mkpts_3d_db, mkpts_query_f, q_hw_i, query_image_scale, query_intrinsic,
     query_pose_gt (and query_intrinsic_origin, query_image_path for ADD) from `data`, estimates the poses with
     configs' point_cloud_rescale / pnp_reprojection_error / use_pycolmap_ransac (`pnp_kwargs`, e.g. solver=, are passed through):
-    ONE `pose.ransac_PnP_batch` call for the solvers "p3p" and "epnp", `pose.ransac_PnP` per sample for "loransac", for ids that
+    ONE `pose.ransac_PnP_batch` call for the solvers "p3p" and "epnp"; for "loransac" `pose.ransac_PnP` per sample, or ONE
+    `pose.loransac_PnP_batch` call with `batch_loransac=True` (same bytes; off by default); `pose.ransac_PnP` per sample for ids that
     are not in the matcher's order and for `ransac_PnP=`, which names another estimator with the reference's signature and
     return tuple and gets numpy matches (the batch call and the loop give the same bytes),
     scores the whole batch in ONE `pose_metrics` call and writes R_errs, t_errs, inliers, the empty *_c lists and pose_pred
@@ -157,6 +165,7 @@ def compute_query_pose_errors(data, configs, training=False, model_vertices=None
     query_pose_gt and the intrinsics are converted to float64 before scoring; where a caller's tensors are float32 the
     reference evaluates part of the sums in float32, and the results then agree to float32 rounding only."""
     ransac_PnP = pnp_kwargs.pop("ransac_PnP", None)
+    batch_loransac = bool(pnp_kwargs.pop("batch_loransac", False))
     host_matches = ransac_PnP is not None           # another estimator gets numpy matches, as the reference's own does
     if ransac_PnP is None:
         from .pose import ransac_PnP
@@ -182,7 +191,7 @@ def compute_query_pose_errors(data, configs, training=False, model_vertices=None
         query_K_origin = _np(data["query_intrinsic_origin"]).astype(np.float64)
         data.update({"ADD": [], "proj2D": []})
 
-    batch = None if host_matches or not B else _batch_poses(data, configs, query_K, pnp_kwargs)
+    batch = None if host_matches or not B else _batch_poses(data, configs, query_K, pnp_kwargs, batch_loransac)
     if batch is not None:
         valid = [bool(s) for s in batch["state"]]
         pose_pred = [batch["pose_homo"][bs] if valid[bs] else np.eye(4) for bs in range(B)]

@@ -3,8 +3,9 @@
 
 Same call signature and return tuple `(pose [3,4], pose_homo [4,4], inliers, state)`; the
 matches may be CUDA tensors (they then never leave the device until the 12-number pose is read)
-or numpy arrays.  Deterministic for a given `seed`.  No CPU fallback.  `ransac_PnP_batch` estimates the poses of a whole batch
-in one pass (csrc/pnp_batch.hip; "p3p" and "epnp"), each sample bit-identical to its single call.
+or numpy arrays.  Deterministic for a given `seed`.  No CPU fallback.  `ransac_PnP_batch` ("p3p" and "epnp", csrc/pnp_batch.hip)
+and `loransac_PnP_batch` ("loransac", csrc/pnp_lo_batch.hip) estimate the poses of a whole batch in one pass, each sample
+bit-identical to its single call.
 
 Three estimators (`solver=`):
   * "epnp": the reference's estimator, OpenCV 4.x `solvePnPRansac(flags=SOLVEPNP_EPNP)` as we read it (OpenCV's source is
@@ -187,84 +188,64 @@ class BatchIdsError(ValueError):
 
 
 def _batch_solver(solver, use_pycolmap_ransac):
-    """the solver a batch call runs ("p3p" / "epnp"); "loransac", named or resolved from "auto", has no batch pass"""
+    """the solver `ransac_PnP_batch` runs ("p3p" / "epnp"); "loransac", named or resolved from "auto", is `loransac_PnP_batch`'s"""
     if solver == "auto":
         solver = "loransac" if use_pycolmap_ransac else "epnp"
     elif solver not in _SOLVER_NAMES:
         raise _bad_solver(solver, _SOLVER_NAMES + ("auto",))
     if solver == "loransac":
-        raise NotImplementedError('ransac_PnP_batch runs "p3p" and "epnp"; LO-RANSAC is per sample: call ransac_PnP(solver="loransac") '
-                                  "or ransac_PnP_ex for each sample")
+        raise NotImplementedError('ransac_PnP_batch runs "p3p" and "epnp"; LO-RANSAC has a batch pass of its own, loransac_PnP_batch '
+                                  '(or call ransac_PnP(solver="loransac") / ransac_PnP_ex for each sample)')
     return solver
 
 
-def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, scale=1, pnp_reprojection_error=5,
-                     iterations=10000, refine_iters=8, seed=0, solver="p3p", confidence=None, device=None,
-                     use_pycolmap_ransac=False):
-    """`ransac_PnP_ex` for B samples in one pass (`opp_pnp_ransac_batch`, csrc/pnp_batch.hip): sample b's results are bit for bit
-    those of `ransac_PnP_ex(K[b], <its matches>, seed=seed[b], ...)`.  K [B,3,3]; pts_2d [M,2] and pts_3d [M,3] hold the matches of
-    all samples concatenated in sample order (CUDA tensors stay on the device); give exactly one of `m_bids` [M] (the matcher's
-    batch ids, non-decreasing, in [0, B)) and `offsets` [B+1] (sample b = matches offsets[b]:offsets[b+1]); seed: an int for every
-    sample, or B of them; solver "p3p", "epnp" or "auto" (with `use_pycolmap_ransac`, as in `ransac_PnP`; "loransac" raises
-    NotImplementedError); confidence None: the solver's default, as in `ransac_PnP_ex`.
-    -> dict: pose [B,3,4] and pose_homo [B,4,4] float64, state [B] bool, stop [B], inliers: B arrays [k,1] int32 of indices LOCAL to
-    the sample (an empty bool array where state is False), pose_dev: the [B,3,4] float64 CUDA tensor.  Two device-to-host copies
-    whatever B is (poses + counts + offsets, and the mask); ids that break the contract raise ValueError after the first."""
-    solver = _batch_solver(solver, use_pycolmap_ransac)
+def _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device):
+    """the argument checks and host-side inputs the batch calls share -> (device, K [B,3,3] float64, seeds [B], p2, p3)"""
     if (m_bids is None) == (offsets is None):
-        raise ValueError("ransac_PnP_batch: give exactly one of m_bids and offsets")
-    if confidence is None:
-        confidence = 0.99 if solver == "epnp" else 1.0
-    lib = _lib.load()
+        raise ValueError("%s: give exactly one of m_bids and offsets" % name)
     if device is None:
         device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
     Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
     Kn = Kn.astype(np.float64).reshape(-1, 3, 3)
     B = int(Kn.shape[0])
     if batch_size is not None and int(batch_size) != B:
-        raise ValueError("ransac_PnP_batch: K holds %d matrices, batch_size is %d" % (B, int(batch_size)))
+        raise ValueError("%s: K holds %d matrices, batch_size is %d" % (name, B, int(batch_size)))
     if not 1 <= B <= 1024:
-        raise ValueError("ransac_PnP_batch: 1 to 1024 samples, got %d" % B)
+        raise ValueError("%s: 1 to 1024 samples, got %d" % (name, B))
     seeds = np.broadcast_to(np.asarray(seed, dtype=np.int64) & 0xFFFFFFFF, (B,)) if np.ndim(seed) == 0 else \
         np.asarray(seed, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
     if seeds.shape != (B,):
-        raise ValueError("ransac_PnP_batch: seed must be an int or %d ints" % B)
+        raise ValueError("%s: seed must be an int or %d ints" % (name, B))
     p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
     p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
-    n = int(p2.shape[0])
-    if int(p3.shape[0]) != n:
-        raise ValueError("ransac_PnP_batch: %d 2D points, %d 3D points" % (n, int(p3.shape[0])))
-    iterations = int(iterations)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
-        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
-        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
-        if m_bids is not None:
-            ids = m_bids if torch.is_tensor(m_bids) else torch.from_numpy(np.ascontiguousarray(m_bids))
-            ids = ids.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
-            if int(ids.shape[0]) != n:
-                raise ValueError("ransac_PnP_batch: %d batch ids for %d matches" % (int(ids.shape[0]), n))
-            off = torch.empty(B + 1, dtype=torch.int32, device=device)
-            _lib.check(lib.opp_pnp_offsets(ids.data_ptr(), n, B, off.data_ptr(), cnt.data_ptr() + 12 * B, stream), "opp_pnp_offsets")
-        else:
-            off = offsets if torch.is_tensor(offsets) else torch.from_numpy(np.ascontiguousarray(offsets))
-            off = off.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
-            if int(off.shape[0]) != B + 1:
-                raise ValueError("ransac_PnP_batch: offsets needs %d entries, got %d" % (B + 1, int(off.shape[0])))
-        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
-        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        nbytes = lib.opp_pnp_batch_workspace_bytes(iterations, B, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.opp_pnp_ransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr(), B, n, K4.data_ptr(), seeds_d.data_ptr(),
-                                            float(pnp_reprojection_error), float(scale), iterations, int(refine_iters),
-                                            _SOLVERS[solver], float(confidence), out.data_ptr(), mask.data_ptr(), cnt.data_ptr(),
-                                            cnt.data_ptr() + 4 * B, cnt.data_ptr() + 8 * B, ws.data_ptr(), nbytes, stream),
-                   "opp_pnp_ransac_batch")
-        host = torch.cat([out.reshape(-1), cnt.double(), off.double()]).cpu().numpy()   # D2H copy 1 of 2
-        if host[12 * B + 3 * B] != 0:
-            raise BatchIdsError("ransac_PnP_batch: m_bids must be non-decreasing with values in [0, %d)" % B)
-        mask_h = mask[:n].cpu().numpy()                                               # D2H copy 2 of 2
+    if int(p3.shape[0]) != int(p2.shape[0]):
+        raise ValueError("%s: %d 2D points, %d 3D points" % (name, int(p2.shape[0]), int(p3.shape[0])))
+    return device, Kn, seeds, p2, p3
+
+
+def _batch_offsets(name, lib, m_bids, offsets, B, n, bad_ptr, device, stream):
+    """offsets [B+1] int32 on the device: from the ids (`opp_pnp_offsets`, which also sets the flag at `bad_ptr`), or the caller's"""
+    if m_bids is not None:
+        ids = m_bids if torch.is_tensor(m_bids) else torch.from_numpy(np.ascontiguousarray(m_bids))
+        ids = ids.to(device=device, dtype=torch.int64).reshape(-1).contiguous()
+        if int(ids.shape[0]) != n:
+            raise ValueError("%s: %d batch ids for %d matches" % (name, int(ids.shape[0]), n))
+        off = torch.empty(B + 1, dtype=torch.int32, device=device)
+        _lib.check(lib.opp_pnp_offsets(ids.data_ptr(), n, B, off.data_ptr(), bad_ptr, stream), "opp_pnp_offsets")
+        return off
+    off = offsets if torch.is_tensor(offsets) else torch.from_numpy(np.ascontiguousarray(offsets))
+    off = off.to(device=device, dtype=torch.int32).reshape(-1).contiguous()
+    if int(off.shape[0]) != B + 1:
+        raise ValueError("%s: offsets needs %d entries, got %d" % (name, B + 1, int(off.shape[0])))
+    return off
+
+
+def _batch_result(name, out, cnt, off, mask, B, n):
+    """the two device-to-host copies of a batch call and the dict it returns; cnt = n_inliers [B], ok [B], stop [B], bad ids"""
+    host = torch.cat([out.reshape(-1), cnt.double(), off.double()]).cpu().numpy()   # D2H copy 1 of 2
+    if host[12 * B + 3 * B] != 0:
+        raise BatchIdsError("%s: m_bids must be non-decreasing with values in [0, %d)" % (name, B))
+    mask_h = mask[:n].cpu().numpy()                                               # D2H copy 2 of 2
     pose = host[:12 * B].reshape(B, 3, 4).copy()
     state = host[13 * B:14 * B] != 0
     stop = host[14 * B:15 * B].astype(np.int64)
@@ -278,6 +259,88 @@ def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=No
         else:
             inliers.append(np.array([]).astype(bool))
     return {"pose": pose, "pose_homo": pose_homo, "state": state, "stop": stop, "inliers": inliers, "pose_dev": out}
+
+
+def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, scale=1, pnp_reprojection_error=5,
+                     iterations=10000, refine_iters=8, seed=0, solver="p3p", confidence=None, device=None,
+                     use_pycolmap_ransac=False):
+    """`ransac_PnP_ex` for B samples in one pass (`opp_pnp_ransac_batch`, csrc/pnp_batch.hip): sample b's results are bit for bit
+    those of `ransac_PnP_ex(K[b], <its matches>, seed=seed[b], ...)`.  K [B,3,3]; pts_2d [M,2] and pts_3d [M,3] hold the matches of
+    all samples concatenated in sample order (CUDA tensors stay on the device); give exactly one of `m_bids` [M] (the matcher's
+    batch ids, non-decreasing, in [0, B)) and `offsets` [B+1] (sample b = matches offsets[b]:offsets[b+1]); seed: an int for every
+    sample, or B of them; solver "p3p", "epnp" or "auto" (with `use_pycolmap_ransac`, as in `ransac_PnP`; "loransac" raises
+    NotImplementedError: `loransac_PnP_batch` is its batch pass); confidence None: the solver's default, as in `ransac_PnP_ex`.
+    -> dict: pose [B,3,4] and pose_homo [B,4,4] float64, state [B] bool, stop [B], inliers: B arrays [k,1] int32 of indices LOCAL to
+    the sample (an empty bool array where state is False), pose_dev: the [B,3,4] float64 CUDA tensor.  Two device-to-host copies
+    whatever B is (poses + counts + offsets, and the mask); ids that break the contract raise ValueError after the first."""
+    name = "ransac_PnP_batch"
+    solver = _batch_solver(solver, use_pycolmap_ransac)
+    device, Kn, seeds, p2, p3 = _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device)
+    if confidence is None:
+        confidence = 0.99 if solver == "epnp" else 1.0
+    lib = _lib.load()
+    B, n = int(Kn.shape[0]), int(p2.shape[0])
+    iterations = int(iterations)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
+        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
+        off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
+        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
+        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        nbytes = lib.opp_pnp_batch_workspace_bytes(iterations, B, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        _lib.check(lib.opp_pnp_ransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr(), B, n, K4.data_ptr(), seeds_d.data_ptr(),
+                                            float(pnp_reprojection_error), float(scale), iterations, int(refine_iters),
+                                            _SOLVERS[solver], float(confidence), out.data_ptr(), mask.data_ptr(), cnt.data_ptr(),
+                                            cnt.data_ptr() + 4 * B, cnt.data_ptr() + 8 * B, ws.data_ptr(), nbytes, stream),
+                   "opp_pnp_ransac_batch")
+        return _batch_result(name, out, cnt, off, mask, B, n)
+
+
+def loransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, pnp_reprojection_error=5, iterations=10000,
+                       seed=0, confidence=None, min_trials=1000, min_inlier_ratio=0.01, simple_pinhole=True, max_batch=128,
+                       device=None):
+    """`ransac_PnP_ex(solver="loransac")` for B samples in one pass (`opp_pnp_loransac_batch`, csrc/pnp_lo_batch.hip): sample b's
+    results are bit for bit those of `ransac_PnP_ex(K[b], <its matches>, seed=seed[b], solver="loransac", ...)`.  The inputs, the
+    errors raised and the dict returned are those of `ransac_PnP_batch`; confidence None: 0.9999; `min_trials`, `min_inlier_ratio`
+    and `simple_pinhole` as in `ransac_PnP_ex` (simple_pinhole True puts K[b,0,0] on both axes, as the reference's pycolmap branch
+    does; that branch applies no `scale`, so there is none here).  A focal length <= 0 raises ValueError.
+    max_batch: samples per C call.  The workspace of a call over b samples and M matches takes about
+    948 * iterations * b + 3496 * M bytes (9.5 MB per sample at 10000 trials: 128 samples -> 1.2 GB), so larger batches run as
+    chunks of `max_batch` samples through the one workspace, enqueued back to back on the same offsets, outputs and mask: no
+    host sync is added and no byte of the result changes.  Two device-to-host copies whatever B and `max_batch` are."""
+    name = "loransac_PnP_batch"
+    device, Kn, seeds, p2, p3 = _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device)
+    fy = Kn[:, 0, 0] if simple_pinhole else Kn[:, 1, 1]
+    if not ((Kn[:, 0, 0] > 0).all() and (fy > 0).all()):
+        raise ValueError("%s: focal lengths must be positive" % name)
+    if int(max_batch) < 1:
+        raise ValueError("%s: max_batch must be at least 1, got %d" % (name, int(max_batch)))
+    if confidence is None:
+        confidence = 0.9999
+    lib = _lib.load()
+    B, n = int(Kn.shape[0]), int(p2.shape[0])
+    iterations, chunk = int(iterations), min(int(max_batch), B)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], fy, Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
+        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
+        off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
+        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
+        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        nbytes = lib.opp_pnp_loransac_batch_workspace_bytes(iterations, chunk, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        for b0 in range(0, B, chunk):                                    # offsets are absolute: a chunk is the same call further on
+            _lib.check(lib.opp_pnp_loransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr() + 4 * b0, min(chunk, B - b0), n,
+                                                  K4.data_ptr() + 32 * b0, seeds_d.data_ptr() + 4 * b0, float(pnp_reprojection_error),
+                                                  iterations, float(confidence), int(min_trials), float(min_inlier_ratio),
+                                                  out.data_ptr() + 96 * b0, mask.data_ptr(), cnt.data_ptr() + 4 * b0,
+                                                  cnt.data_ptr() + 4 * (B + b0), cnt.data_ptr() + 4 * (2 * B + b0), ws.data_ptr(), nbytes,
+                                                  stream), "opp_pnp_loransac_batch")
+        return _batch_result(name, out, cnt, off, mask, B, n)
 
 
 def ransac_PnP(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, img_hw=None, use_pycolmap_ransac=False,
