@@ -557,7 +557,10 @@ int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_points, const d
  * niters = RANSACUpdateNumIters after each new best; the result is that of the sequential loop over hypotheses 0, 1, ...
  * Extra device outputs: stop_out (1 int: hypotheses the sequential loop evaluates), and, when not NULL, samples_out
  * [iterations][5] (sample indices; -1 in the 5th column for P3P) and scores_out [iterations] (inlier counts, -1 = no model),
- * written whenever hypotheses are drawn (n >= 4; with solver 1 not for n == 5). */
+ * written whenever hypotheses are drawn (n >= 4; with solver 1 not for n == 5).
+ * Workspaces: the three P3P / EPnP entries share one layout (opp_pnp_layout, csrc/pnp_batch.h): per sample the hypotheses, their
+ * validity, the scores and the scores masked past the stop index, then 13 doubles per match for the refit.  This entry's is
+ * the batch's at n_samples = 1; opp_pnp_ransac's is its leading part (no masked scores, no refit). */
 size_t opp_pnp_ex_workspace_bytes(int iterations, int n_points);
 int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, const double* K4,
                       double reproj_error_px, double scale, int iterations, unsigned seed,
@@ -626,7 +629,8 @@ int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_points, const
  * and seeds[b]; a failed sample (fewer than 3 matches, no model, too few inliers) gets the identity pose, a zeroed mask segment,
  * ok = 0, n_inliers = 0 (and stop = 0 with fewer than 3 matches).  n_total = 0 is legal (every sample fails).  A focal length
  * <= 0 cannot be refused here (K4 is on the device): the caller checks it.  There are no record outputs.  The workspace holds
- * about 948 * iterations bytes per sample plus 3496 bytes per match; one that is too small is refused before any launch. */
+ * about 948 * iterations bytes per sample plus 3496 bytes per match (opp_lo_batch_layout, csrc/pnp_lo_batch.h; opp_pnp_loransac's
+ * is the same layout at n_samples = 1); one that is too small is refused before any launch. */
 size_t opp_pnp_loransac_batch_workspace_bytes(int iterations, int n_samples, int n_total);
 int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, const int* offsets, int n_samples, int n_total,
                            const double* K4, const unsigned* seeds, double reproj_error_px, int iterations,

@@ -21,8 +21,12 @@
 //                   per-hypothesis counts in index order, skipping 256ths of the range whose maximum cannot be a new best),
 //                   the best hypothesis's inlier mask, and an EPnP refit on those inliers (reductions in point order)
 //
-// The kernel bodies live in pnp_body.h, which the batched kernels (pnp_batch.hip) call as well.
+// The kernel bodies live in pnp_body.h, which the batched kernels (pnp_batch.hip) call as well.  Both entries are one launch
+// routine (pnp_launch); what a sample of n matches runs and where its buffers lie in the workspace are opp_pnp_mode and
+// opp_pnp_layout of pnp_batch.h, which the batch reads too.
 #include "opp_common.h"
+#include "pnp_args.h"
+#include "pnp_batch.h"
 #include "pnp_body.h"
 
 namespace {
@@ -84,18 +88,30 @@ __global__ __launch_bounds__(256) void pnp_epnp_final_kernel(const float* __rest
 }  // namespace
 
 extern "C" size_t opp_pnp_workspace_bytes(int iterations) {
-  return opp_align((size_t)iterations * 12 * sizeof(double)) + 2 * opp_align((size_t)iterations * sizeof(int)) + 1024;
+  if (iterations < 1) return 1024;   // no slab is rounded up to a trial here, unlike in opp_pnp_ex_workspace_bytes
+  OppPnpLayout L;
+  opp_pnp_layout(iterations, 1, 1, &L);
+  return L.score2 + 1024;   // hyp | valid | score
 }
 
-extern "C" int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_points, const double* K4, double reproj_error_px,
-                              double scale, int iterations, unsigned seed, int refine_iters, double* pose_out,
-                              int* inlier_mask, int* n_inliers, int* ok, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  // no matches at all (an empty tensor has no address) is the n < 4 failure below, as in opp_pnp_ransac_ex
-  OPP_CHECK_ARG((n_points == 0 || (pts2d && pts3d)) && n_points >= 0 && K4 && pose_out && inlier_mask && n_inliers && ok && ws,
-                "pnp: null argument");
-  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && scale > 0, "pnp: bad parameters");
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_workspace_bytes(iterations), "pnp: workspace too small");
+extern "C" size_t opp_pnp_ex_workspace_bytes(int iterations, int n_points) { return opp_pnp_layout(iterations, 1, n_points, nullptr); }
+
+namespace {
+
+struct PnpBuffers {   // the workspace, carved (opp_pnp_layout at B = 1); opp_pnp_ransac's ends before score2
+  double* hyp;
+  int *valid, *score, *score2;
+  double* pts;
+};
+
+PnpBuffers pnp_carve(void* ws, int iterations, int n_points) {
+  OppPnpLayout L;
+  opp_pnp_layout(iterations, 1, n_points, &L);
+  char* base = (char*)ws;
+  return {(double*)(base + L.hyp), (int*)(base + L.valid), (int*)(base + L.score), (int*)(base + L.score2), (double*)(base + L.pts)};
+}
+
+PnpParams pnp_params(const double* K4, double reproj_error_px, double scale, int n_points, int iterations, unsigned seed) {
   PnpParams prm;
   for (int k = 0; k < 4; ++k) prm.K4[k] = K4[k];
   prm.thr2 = reproj_error_px * reproj_error_px;
@@ -103,82 +119,76 @@ extern "C" int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_poin
   prm.n = n_points;
   prm.iters = iterations;
   prm.seed = seed;
-  char* base = (char*)ws;
-  double* hyp = (double*)base;
-  int* valid = (int*)(base + opp_align((size_t)iterations * 12 * sizeof(double)));
-  int* score = (int*)((char*)valid + opp_align((size_t)iterations * sizeof(int)));
-  if (n_points < 4) {   // cv2.solvePnPRansac raises -> reference returns identity / no inliers / state False
-    prm.iters = 0;
-    (void)hipMemsetAsync(score, 0, sizeof(int), stream);
-  } else {
-    hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid);
-    hipLaunchKernelGGL(pnp_score_kernel, dim3(opp_cdiv(iterations, 4)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid, score);
-  }
-  hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, score, refine_iters, pose_out,
-                     inlier_mask, n_inliers, ok);
-  OPP_CHECK_LAUNCH("pnp kernels");
-  return OPP_OK;
+  return prm;
 }
 
-extern "C" size_t opp_pnp_ex_workspace_bytes(int iterations, int n_points) {
-  if (iterations < 1) iterations = 1;
-  if (n_points < 1) n_points = 1;
-  return opp_align((size_t)iterations * 12 * sizeof(double)) + 3 * opp_align((size_t)iterations * sizeof(int)) +
-         opp_align((size_t)n_points * 13 * sizeof(double)) + 1024;
+// The launches of both entries; what a sample of prm.n matches runs is opp_pnp_mode's table.  stop_stage: solver 0 masks the
+// hypotheses past the stop index (into b.score2) before the refinement; without it b.score2 and b.pts are not touched.
+// stop_out, samples_out, scores_out: optional.  -> false when the copy of the scores could not be enqueued
+bool pnp_launch(hipStream_t stream, const float* pts2d, const float* pts3d, PnpParams prm, const PnpBuffers& b, int solver, bool stop_stage,
+                double confidence, int refine_iters, double* pose_out, int* inlier_mask, int* n_inliers, int* ok, int* stop_out,
+                int* samples_out, int* scores_out) {
+  const int iterations = prm.iters;
+  int m;
+  const int mode = opp_pnp_mode(solver, prm.n, &m);
+  if (mode == OPP_PNP_P3P_RANSAC || mode == OPP_PNP_EPNP_RANSAC) {
+    if (mode == OPP_PNP_EPNP_RANSAC)
+      hipLaunchKernelGGL(pnp_epnp_hypotheses_kernel, dim3(iterations), dim3(64), 0, stream, pts2d, pts3d, prm, b.hyp, b.valid, samples_out);
+    else
+      hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, pts2d, pts3d, prm, b.hyp, b.valid);
+    hipLaunchKernelGGL(pnp_score_kernel, dim3(opp_cdiv(iterations, 4)), dim3(256), 0, stream, pts2d, pts3d, prm, b.hyp, b.valid, b.score);
+    if (samples_out && mode == OPP_PNP_P3P_RANSAC)
+      hipLaunchKernelGGL(pnp_p3p_samples_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, prm, samples_out);
+    if (scores_out && hipMemcpyAsync(scores_out, b.score, (size_t)iterations * sizeof(int), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return false;
+  }
+  if (solver == 0) {
+    const int* score = b.score;
+    if (mode == OPP_PNP_FAIL) {   // cv2.solvePnPRansac raises -> reference returns identity / no inliers / state False
+      prm.iters = 0;
+      (void)hipMemsetAsync(b.score, 0, sizeof(int), stream);
+      if (stop_out) (void)hipMemsetAsync(stop_out, 0, sizeof(int), stream);
+    } else if (stop_stage) {   // the refinement sees only the hypotheses before the stop index
+      hipLaunchKernelGGL(pnp_stop_kernel, dim3(1), dim3(256), 0, stream, b.score, prm, m, confidence, b.score2, stop_out);
+      score = b.score2;
+    }
+    hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, b.hyp, score, refine_iters, pose_out, inlier_mask,
+                       n_inliers, ok);
+  } else {
+    hipLaunchKernelGGL(pnp_epnp_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, b.hyp, b.score, opp_pnp_final_mode(mode), m,
+                       confidence, b.pts, pose_out, inlier_mask, n_inliers, ok, stop_out);
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_points, const double* K4, double reproj_error_px,
+                              double scale, int iterations, unsigned seed, int refine_iters, double* pose_out,
+                              int* inlier_mask, int* n_inliers, int* ok, void* ws, size_t ws_bytes, void* stream_) {
+  OPP_TRY(opp_pnp_check_args("pnp", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px, scale > 0,
+                             1.0));
+  OPP_CHECK_ARG(ws_bytes >= opp_pnp_workspace_bytes(iterations), "pnp: workspace too small");
+  // solver 0 over every hypothesis: no stop stage, no optional output
+  pnp_launch((hipStream_t)stream_, pts2d, pts3d, pnp_params(K4, reproj_error_px, scale, n_points, iterations, seed),
+             pnp_carve(ws, iterations, n_points), 0, false, 1.0, refine_iters, pose_out, inlier_mask, n_inliers, ok, nullptr, nullptr, nullptr);
+  OPP_CHECK_LAUNCH("pnp kernels");
+  return OPP_OK;
 }
 
 extern "C" int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_points, const double* K4, double reproj_error_px,
                                  double scale, int iterations, unsigned seed, int refine_iters, int solver, double confidence,
                                  double* pose_out, int* inlier_mask, int* n_inliers, int* ok, int* stop_out, int* samples_out,
                                  int* scores_out, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  OPP_CHECK_ARG((n_points == 0 || (pts2d && pts3d)) && n_points >= 0 && K4 && pose_out && inlier_mask && n_inliers && ok && ws,
-                "pnp_ex: null argument");
-  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && scale > 0, "pnp_ex: bad parameters");
-  OPP_CHECK_ARG(solver == 0 || solver == 1, "pnp_ex: solver must be 0 (P3P) or 1 (EPnP)");
-  OPP_CHECK_ARG(confidence > 0.0, "pnp_ex: confidence must be > 0 (>= 1: no early stop)");
+  OPP_TRY(opp_pnp_check_args("pnp_ex", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
+                             scale > 0, confidence));
+  OPP_TRY(opp_pnp_check_solver("pnp_ex", solver));
   OPP_CHECK_ARG(ws_bytes >= opp_pnp_ex_workspace_bytes(iterations, n_points), "pnp_ex: workspace too small");
-  PnpParams prm;
-  for (int k = 0; k < 4; ++k) prm.K4[k] = K4[k];
-  prm.thr2 = reproj_error_px * reproj_error_px;
-  prm.scale = scale;
-  prm.n = n_points;
-  prm.iters = iterations;
-  prm.seed = seed;
-  char* base = (char*)ws;
-  double* hyp = (double*)base;
-  int* valid = (int*)(base + opp_align((size_t)iterations * 12 * sizeof(double)));
-  int* score = (int*)((char*)valid + opp_align((size_t)iterations * sizeof(int)));
-  int* score2 = (int*)((char*)score + opp_align((size_t)iterations * sizeof(int)));
-  double* pts = (double*)((char*)score2 + opp_align((size_t)iterations * sizeof(int)));
-  const bool sample = solver == 0 ? n_points >= 4 : (n_points == 4 || n_points >= 6);
-  if (sample) {
-    if (solver == 1 && n_points >= 6)
-      hipLaunchKernelGGL(pnp_epnp_hypotheses_kernel, dim3(iterations), dim3(64), 0, stream, pts2d, pts3d, prm, hyp, valid, samples_out);
-    else
-      hipLaunchKernelGGL(pnp_hypotheses_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid);
-    hipLaunchKernelGGL(pnp_score_kernel, dim3(opp_cdiv(iterations, 4)), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, valid, score);
-    if (samples_out && !(solver == 1 && n_points >= 6))
-      hipLaunchKernelGGL(pnp_p3p_samples_kernel, dim3(opp_cdiv(iterations, 256)), dim3(256), 0, stream, prm, samples_out);
-    if (scores_out && hipMemcpyAsync(scores_out, score, (size_t)iterations * sizeof(int), hipMemcpyDeviceToDevice, stream) != hipSuccess) {
-      opp_set_error("pnp_ex: copy of the scores failed");
-      return OPP_ERR_LAUNCH;
-    }
-  }
-  if (solver == 0) {   // opp_pnp_ransac's launches; the refinement sees only the hypotheses before the stop index
-    if (!sample) {
-      prm.iters = 0;
-      (void)hipMemsetAsync(score, 0, sizeof(int), stream);
-      if (stop_out) (void)hipMemsetAsync(stop_out, 0, sizeof(int), stream);
-    } else {
-      hipLaunchKernelGGL(pnp_stop_kernel, dim3(1), dim3(256), 0, stream, score, prm, 4, confidence, score2, stop_out);
-    }
-    hipLaunchKernelGGL(pnp_refine_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, sample ? score2 : score, refine_iters,
-                       pose_out, inlier_mask, n_inliers, ok);
-  } else {
-    const int mode = n_points < 4 ? 3 : (n_points == 4 ? 0 : (n_points == 5 ? 2 : 1));
-    hipLaunchKernelGGL(pnp_epnp_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, hyp, score, mode, n_points == 4 ? 4 : 5,
-                       confidence, pts, pose_out, inlier_mask, n_inliers, ok, stop_out);
+  if (!pnp_launch((hipStream_t)stream_, pts2d, pts3d, pnp_params(K4, reproj_error_px, scale, n_points, iterations, seed),
+                  pnp_carve(ws, iterations, n_points), solver, true, confidence, refine_iters, pose_out, inlier_mask, n_inliers, ok, stop_out,
+                  samples_out, scores_out)) {
+    opp_set_error("pnp_ex: copy of the scores failed");
+    return OPP_ERR_LAUNCH;
   }
   OPP_CHECK_LAUNCH("pnp_ex kernels");
   return OPP_OK;

@@ -1,7 +1,9 @@
-// The two pieces of pure logic of the batched PnP-RANSAC (pnp_batch.hip), written once for the device and the host
-// (compiled with g++: tests/test_pnp_batch_cpu.py): the sample boundaries from the matcher's batch ids, and what a sample
-// of n matches runs under a solver -- the decisions opp_pnp_ransac_ex takes on the host from n_points.
+// The pure logic of the P3P / EPnP PnP-RANSAC, written once for the device and the host (compiled with g++:
+// tests/test_pnp_batch_cpu.py): what a sample of n matches runs under a solver -- the one table opp_pnp_ransac_ex reads on the
+// host from n_points and the batched kernels (pnp_batch.hip) read per sample --, the layout of the workspace of the single
+// calls (pnp.hip, B = 1) and of the batch, and the sample boundaries from the matcher's batch ids.
 #pragma once
+#include <stddef.h>
 
 #if defined(__HIPCC__)
 #define OPP_BHD __host__ __device__ inline
@@ -23,6 +25,40 @@ OPP_BHD int opp_pnp_mode(int solver, int n, int* m) {
   if (n < 4) return OPP_PNP_FAIL;
   if (solver == 0 || n == 4) return OPP_PNP_P3P_RANSAC;
   return n == 5 ? OPP_PNP_EPNP_ONE : OPP_PNP_EPNP_RANSAC;
+}
+
+// the mode number of solver 1's final stage (pnp_epnp_final_body) for what opp_pnp_mode returned
+OPP_BHD int opp_pnp_final_mode(int mode) {
+  return mode == OPP_PNP_FAIL ? 3 : (mode == OPP_PNP_P3P_RANSAC ? 0 : (mode == OPP_PNP_EPNP_ONE ? 2 : 1));
+}
+
+OPP_BHD size_t opp_ws_align(size_t x) { return (x + 255) / 256 * 256; }
+
+// byte offsets into the workspace: hyp | valid | score | score2 | pts.  The first four are per-sample slabs, sample b's at
+// <array> + b * <stride>; the EPnP refit's points follow the matches, sample b's 13 * offsets[b] doubles into pts.
+// opp_pnp_ransac needs hyp | valid | score alone, the bytes before score2 (at B = 1).
+struct OppPnpLayout {
+  size_t hyp, valid, score, score2, pts;
+  size_t hyp_stride;   // hyp: [iterations][12] doubles, R | t
+  size_t int_stride;   // valid, score, score2: [iterations] ints
+  size_t bytes;
+};
+
+OPP_BHD size_t opp_pnp_layout(int iterations, int n_samples, int n_total, OppPnpLayout* L) {
+  const size_t I = (size_t)(iterations < 1 ? 1 : iterations), B = (size_t)(n_samples < 1 ? 1 : n_samples);
+  const size_t n = (size_t)(n_total < 1 ? 1 : n_total);
+  OppPnpLayout l;
+  l.hyp_stride = opp_ws_align(I * 12 * sizeof(double));
+  l.int_stride = opp_ws_align(I * sizeof(int));
+  size_t off = 0;
+  l.hyp = off, off += B * l.hyp_stride;
+  l.valid = off, off += B * l.int_stride;
+  l.score = off, off += B * l.int_stride;
+  l.score2 = off, off += B * l.int_stride;
+  l.pts = off, off += opp_ws_align(n * 13 * sizeof(double));
+  l.bytes = off + 1024;
+  if (L) *L = l;
+  return l.bytes;
 }
 
 // first index i in [0, n) with ids[i] >= key (n when there is none); ids non-decreasing

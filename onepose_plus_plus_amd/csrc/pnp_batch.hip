@@ -3,11 +3,11 @@
 // tails (pnp_refine_kernel / pnp_epnp_final_kernel) with a device-to-host copy after each.
 //
 // The matches of all samples lie concatenated in sample order, delimited by a device array offsets [B+1]: the sizes n_b are
-// known on the device only, so everything opp_pnp_ransac_ex decides on the host from n_points -- whether hypotheses are drawn,
-// which minimal solver draws them, m, the mode of the final stage, the n < 4 failure -- is decided per sample in the kernels
+// known on the device only, so the table opp_pnp_ransac_ex reads on the host from n_points -- whether hypotheses are drawn,
+// which minimal solver draws them, m, the mode of the final stage, the n < 4 failure -- is read per sample in the kernels
 // (opp_pnp_mode, pnp_batch.h), and a workgroup whose sample does not use a kernel returns at once.  Each sample reads its own
 // K4 and seed from device arrays and owns an `iterations`-sized slab of hyp / valid / score / score2; the EPnP refit's points
-// of sample b start at 13 * offsets[b] doubles of one 13 * n_total array.  Offsets that do not describe a segment of
+// of sample b start at 13 * offsets[b] doubles of one 13 * n_total array (opp_pnp_layout).  Offsets that do not describe a segment of
 // [0, n_total] make an empty sample (opp_pnp_extent): nothing is read or written outside the caller's arrays.
 //
 //   grid (ceil(iters / 256), B)  pnp_batch_hypotheses_kernel       P3P hypotheses (solver 0; solver 1 when n == 4)
@@ -17,6 +17,7 @@
 //
 // Per sample the result is that of opp_pnp_ransac_ex on its slice, bit for bit (tests/test_pnp_batch_gpu.py).
 #include "opp_common.h"
+#include "pnp_args.h"
 #include "pnp_batch.h"
 #include "pnp_body.h"
 
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void pnp_batch_refine_kernel(PnpBatch a) {
 __global__ __launch_bounds__(256) void pnp_batch_epnp_final_kernel(PnpBatch a) {
   const int b = blockIdx.x;
   const PnpSample s = pnp_load_sample(a, b);
-  const int mode = s.mode == OPP_PNP_FAIL ? 3 : (s.mode == OPP_PNP_P3P_RANSAC ? 0 : (s.mode == OPP_PNP_EPNP_ONE ? 2 : 1));
+  const int mode = opp_pnp_final_mode(s.mode);
   __shared__ PnpParams s_prm;   // as in pnp_batch_epnp_hypotheses_kernel
   if (threadIdx.x == 0) s_prm = s.prm;
   __syncthreads();
@@ -128,17 +129,10 @@ __global__ __launch_bounds__(256) void pnp_batch_epnp_final_kernel(PnpBatch a) {
                       a.stop + b);
 }
 
-size_t hyp_slab_bytes(int iterations) { return opp_align((size_t)iterations * 12 * sizeof(double)); }
-size_t int_slab_bytes(int iterations) { return opp_align((size_t)iterations * sizeof(int)); }
-
 }  // namespace
 
 extern "C" size_t opp_pnp_batch_workspace_bytes(int iterations, int n_samples, int n_total) {
-  if (iterations < 1) iterations = 1;
-  if (n_samples < 1) n_samples = 1;
-  if (n_total < 1) n_total = 1;
-  return (size_t)n_samples * (hyp_slab_bytes(iterations) + 3 * int_slab_bytes(iterations)) + opp_align((size_t)n_total * 13 * sizeof(double)) +
-         1024;
+  return opp_pnp_layout(iterations, n_samples, n_total, nullptr);
 }
 
 extern "C" int opp_pnp_offsets(const long long* m_bids, int n_total, int n_samples, int* offsets, int* bad, void* stream_) {
@@ -160,13 +154,10 @@ extern "C" int opp_pnp_ransac_batch(const float* pts2d, const float* pts3d, cons
                                     int refine_iters, int solver, double confidence, double* pose_out, int* inlier_mask,
                                     int* n_inliers, int* ok, int* stop, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  OPP_CHECK_ARG((n_total == 0 || (pts2d && pts3d)) && n_total >= 0 && offsets && K4 && seeds && pose_out && inlier_mask && n_inliers &&
-                    ok && stop && ws,
-                "pnp_batch: null argument");
-  OPP_CHECK_ARG(n_samples >= 1 && n_samples <= 1024, "pnp_batch: n_samples must be in [1, 1024]");
-  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && scale > 0, "pnp_batch: bad parameters");
-  OPP_CHECK_ARG(solver == 0 || solver == 1, "pnp_batch: solver must be 0 (P3P) or 1 (EPnP)");
-  OPP_CHECK_ARG(confidence > 0.0, "pnp_batch: confidence must be > 0 (>= 1: no early stop)");
+  OPP_TRY(opp_pnp_check_batch("pnp_batch", n_samples, offsets, seeds, stop));
+  OPP_TRY(opp_pnp_check_args("pnp_batch", pts2d, pts3d, n_total, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
+                             scale > 0, confidence));
+  OPP_TRY(opp_pnp_check_solver("pnp_batch", solver));
   OPP_CHECK_ARG(ws_bytes >= opp_pnp_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_batch: workspace too small");
   PnpBatch a;
   a.p2 = pts2d;
@@ -181,15 +172,16 @@ extern "C" int opp_pnp_ransac_batch(const float* pts2d, const float* pts3d, cons
   a.iters = iterations;
   a.solver = solver;
   a.refine_iters = refine_iters;
-  const size_t B = (size_t)n_samples;
+  OppPnpLayout L;
+  opp_pnp_layout(iterations, n_samples, n_total, &L);
   char* base = (char*)ws;
-  a.hyp = (double*)base;
-  a.valid = (int*)(base + B * hyp_slab_bytes(iterations));
-  a.score = (int*)((char*)a.valid + B * int_slab_bytes(iterations));
-  a.score2 = (int*)((char*)a.score + B * int_slab_bytes(iterations));
-  a.pts = (double*)((char*)a.score2 + B * int_slab_bytes(iterations));
-  a.hyp_stride = hyp_slab_bytes(iterations) / sizeof(double);
-  a.int_stride = int_slab_bytes(iterations) / sizeof(int);
+  a.hyp = (double*)(base + L.hyp);
+  a.valid = (int*)(base + L.valid);
+  a.score = (int*)(base + L.score);
+  a.score2 = (int*)(base + L.score2);
+  a.pts = (double*)(base + L.pts);
+  a.hyp_stride = L.hyp_stride / sizeof(double);
+  a.int_stride = L.int_stride / sizeof(int);
   a.pose_out = pose_out;
   a.mask = inlier_mask;
   a.n_inl = n_inliers;

@@ -18,7 +18,9 @@
 // launches over the remaining trials read it and return early past it.  Every loop has a fixed bound, no workgroup waits on
 // another, and all arrays live in LDS or in the workspace (no private-segment memory).
 // The kernels below are wrappers: their bodies are in pnp_lo_body.h, which the batched kernels of pnp_lo_batch.hip call too.
+// The workspace is the batch's at one sample (opp_lo_batch_layout, pnp_lo_batch.h, with opp_lo_mode and opp_lo_first_pass).
 #include "opp_common.h"
+#include "pnp_args.h"
 #include "pnp_lo_body.h"
 
 namespace {
@@ -57,61 +59,19 @@ __global__ __launch_bounds__(256) void loransac_final_kernel(const float* __rest
   lo_final_body(p2, p3, prm, mode, b, pose_out, mask, n_inl, ok_out, stop_out, rec);
 }
 
-size_t lo_layout(int iterations, int n_points, char* base, LoBuffers* b) {
-  const size_t I = (size_t)(iterations < 1 ? 1 : iterations), n = (size_t)(n_points < 1 ? 1 : n_points);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += opp_align(bytes);
-    return p;
-  };
-  char* hyp = take(I * 48 * sizeof(double));
-  char* nmod = take(I * sizeof(int));
-  char* cnt = take(I * 4 * sizeof(int));
-  char* sum = take(I * 4 * sizeof(double));
-  char* cand_idx = take(I * 4 * sizeof(int));
-  char* cand_rc = take(I * 4 * sizeof(int));
-  char* cand_rs = take(I * 4 * sizeof(double));
-  char* cand_lc = take(I * 4 * sizeof(int));
-  char* cand_ls = take(I * 4 * sizeof(double));
-  char* cand_pose = take(I * 48 * sizeof(double));
-  char* cand_taken = take(I * 4 * sizeof(int));
-  char* ctl = take(64);
-  char* lo_pts = take((size_t)kLoGrid * 13 * n * sizeof(double));
-  char* fin_pts = take((size_t)(5 + OPP_LM_ROW) * n * sizeof(double));
-  if (b) {
-    b->hyp = (double*)hyp;
-    b->nmod = (int*)nmod;
-    b->cnt = (int*)cnt;
-    b->sum = (double*)sum;
-    b->cand_idx = (int*)cand_idx;
-    b->cand_rc = (int*)cand_rc;
-    b->cand_rs = (double*)cand_rs;
-    b->cand_lc = (int*)cand_lc;
-    b->cand_ls = (double*)cand_ls;
-    b->cand_pose = (double*)cand_pose;
-    b->cand_taken = (int*)cand_taken;
-    b->ctl = (int*)ctl;
-    b->lo_pts = (double*)lo_pts;
-    b->fin_pts = (double*)fin_pts;
-  }
-  return off;
-}
-
 }  // namespace
 
-extern "C" size_t opp_pnp_loransac_workspace_bytes(int iterations, int n_points) { return lo_layout(iterations, n_points, nullptr, nullptr); }
+extern "C" size_t opp_pnp_loransac_workspace_bytes(int iterations, int n_points) {
+  return opp_lo_batch_layout(iterations, 1, n_points, nullptr);
+}
 
 extern "C" int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_points, const double* K4, double reproj_error_px,
                                 int iterations, unsigned seed, double confidence, int min_trials, double min_inlier_ratio, double* pose_out,
                                 int* inlier_mask, int* n_inliers, int* ok, int* stop_out, const OppLoRecord* record, void* ws, size_t ws_bytes,
                                 void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  OPP_CHECK_ARG((n_points == 0 || (pts2d && pts3d)) && n_points >= 0 && K4 && pose_out && inlier_mask && n_inliers && ok && ws,
-                "pnp_loransac: null argument");
-  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && min_trials >= 0 && min_inlier_ratio >= 0.0,
-                "pnp_loransac: bad parameters");
-  OPP_CHECK_ARG(confidence > 0.0, "pnp_loransac: confidence must be > 0 (>= 1: no early stop)");
+  OPP_TRY(opp_pnp_check_args("pnp_loransac", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
+                             min_trials >= 0 && min_inlier_ratio >= 0.0, confidence));
   OPP_CHECK_ARG(K4[0] > 0.0 && K4[1] > 0.0, "pnp_loransac: focal lengths must be positive");
   OPP_CHECK_ARG(ws_bytes >= opp_pnp_loransac_workspace_bytes(iterations, n_points), "pnp_loransac: workspace too small");
   LoParams prm;
@@ -123,25 +83,24 @@ extern "C" int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_po
   prm.iters = iterations;
   prm.min_trials = min_trials;
   prm.seed = seed;
-  LoBuffers b;
-  lo_layout(iterations, n_points, (char*)ws, &b);
-  OppLoRecord rec;
-  memset(&rec, 0, sizeof(rec));
-  if (record) rec = *record;
-  if (n_points < 3) {   // pycolmap reports failure: identity / no inliers / state False
+  OppLoBatchLayout L;
+  opp_lo_batch_layout(iterations, 1, n_points, &L);
+  const LoBuffers b = lo_buffers((char*)ws, L, 0, 0);
+  const OppLoRecord rec = record ? *record : OppLoRecord{};
+  if (opp_lo_mode(n_points) == OPP_LO_FAIL) {   // pycolmap reports failure: identity / no inliers / state False
     hipLaunchKernelGGL(loransac_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, 2, b, pose_out, inlier_mask, n_inliers, ok,
                        stop_out, rec);
     OPP_CHECK_LAUNCH("pnp_loransac kernels");
     return OPP_OK;
   }
-  const int t1 = min_trials < iterations ? (min_trials > 0 ? min_trials : 1) : iterations;
+  const int t1 = opp_lo_first_pass(min_trials, iterations);
   // first pass: the trials every run evaluates
   hipLaunchKernelGGL(loransac_hypotheses_kernel, dim3(opp_cdiv(t1, 256)), dim3(256), 0, stream, pts2d, pts3d, prm, 0, t1, (const int*)nullptr,
                      b.hyp, b.nmod, rec.samples);
   hipLaunchKernelGGL(loransac_score_kernel, dim3(t1), dim3(256), 0, stream, pts2d, pts3d, prm, 0, t1, (const int*)nullptr, b.hyp, b.nmod, b.cnt,
                      b.sum, rec);
   hipLaunchKernelGGL(loransac_candidates_kernel, dim3(1), dim3(256), 0, stream, t1, (const int*)nullptr, -1, b);
-  hipLaunchKernelGGL(loransac_optimise_kernel, dim3(kLoGrid), dim3(64), 0, stream, pts2d, pts3d, prm, (const int*)nullptr, -1, b);
+  hipLaunchKernelGGL(loransac_optimise_kernel, dim3(OPP_LO_GRID), dim3(64), 0, stream, pts2d, pts3d, prm, (const int*)nullptr, -1, b);
   if (t1 < iterations) {   // the trials up to the first pass's bound (read on the device; nothing runs past it)
     const int* bound = b.ctl + 1;
     hipLaunchKernelGGL(loransac_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, 0, b, pose_out, inlier_mask, n_inliers, ok,
@@ -151,7 +110,7 @@ extern "C" int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_po
     hipLaunchKernelGGL(loransac_score_kernel, dim3(iterations - t1), dim3(256), 0, stream, pts2d, pts3d, prm, t1, iterations, bound, b.hyp, b.nmod,
                        b.cnt, b.sum, rec);
     hipLaunchKernelGGL(loransac_candidates_kernel, dim3(1), dim3(256), 0, stream, iterations, bound, t1, b);
-    hipLaunchKernelGGL(loransac_optimise_kernel, dim3(kLoGrid), dim3(64), 0, stream, pts2d, pts3d, prm, bound, t1, b);
+    hipLaunchKernelGGL(loransac_optimise_kernel, dim3(OPP_LO_GRID), dim3(64), 0, stream, pts2d, pts3d, prm, bound, t1, b);
   }
   hipLaunchKernelGGL(loransac_final_kernel, dim3(1), dim3(256), 0, stream, pts2d, pts3d, prm, 1, b, pose_out, inlier_mask, n_inliers, ok, stop_out,
                      rec);

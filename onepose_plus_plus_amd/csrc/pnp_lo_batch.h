@@ -1,14 +1,16 @@
-// The pure logic of the batched LO-RANSAC (pnp_lo_batch.hip), written once for the device and the host (compiled with g++:
-// tests/test_loransac_batch_cpu.py): what a sample of n matches runs -- the one decision opp_pnp_loransac takes on the host from
-// n_points --, the trials of the first pass, and the layout of the one workspace that holds every sample's buffers.
+// The pure logic of LO-RANSAC, written once for the device and the host (compiled with g++: tests/test_loransac_batch_cpu.py):
+// what a sample of n matches runs -- opp_pnp_loransac (pnp_lo.hip) asks on the host, the batched kernels (pnp_lo_batch.hip) per
+// sample --, the trials of the first pass, and the layout of the one workspace that holds every sample's buffers (B = 1: the
+// single call's).
 #pragma once
 #include <stddef.h>
 
-#include "pnp_batch.h"   // OPP_BHD, opp_pnp_extent
+#include "pnp_batch.h"   // OPP_BHD, opp_ws_align, opp_pnp_extent
+#include "pnp_math.h"    // OPP_LM_ROW
 
-#define OPP_LO_GRID 32      // LO workgroups per sample (kLoGrid of pnp_lo_body.h)
-#define OPP_LO_PTS_ROW 13   // doubles per match and LO workgroup: X[3], uv[2], alphas[4], pcs[3], err
-#define OPP_LO_FIN_ROW 21   // doubles per match of the final stage: X[3], uv[2] and a row of the refinement (5 + OPP_LM_ROW)
+#define OPP_LO_GRID 32                     // LO workgroups per sample, each with its own OPP_LO_PTS_ROW * n doubles
+#define OPP_LO_PTS_ROW 13                  // doubles per match and LO workgroup: X[3], uv[2], alphas[4], pcs[3], err
+#define OPP_LO_FIN_ROW (5 + OPP_LM_ROW)    // doubles per match of the final stage: X[3], uv[2] and a row of the refinement
 
 // what a sample runs
 enum OppLoMode {
@@ -22,8 +24,6 @@ OPP_BHD int opp_lo_mode(int n) { return n < 3 ? OPP_LO_FAIL : OPP_LO_RUN; }
 OPP_BHD int opp_lo_first_pass(int min_trials, int iterations) {
   return min_trials < iterations ? (min_trials > 0 ? min_trials : 1) : iterations;
 }
-
-OPP_BHD size_t opp_lo_align(size_t x) { return (x + 255) / 256 * 256; }
 
 // byte offsets into the workspace.  The arrays that scale with the trials are per-sample slabs: sample b's starts at
 // <array> + b * <stride>.  The point arrays follow the matches: sample b's LO region starts OPP_LO_GRID * OPP_LO_PTS_ROW *
@@ -42,10 +42,10 @@ OPP_BHD size_t opp_lo_batch_layout(int iterations, int n_samples, int n_total, O
   const size_t I = (size_t)(iterations < 1 ? 1 : iterations), B = (size_t)(n_samples < 1 ? 1 : n_samples);
   const size_t n = (size_t)(n_total < 1 ? 1 : n_total);
   OppLoBatchLayout l;
-  l.pose_stride = opp_lo_align(I * 48 * sizeof(double));
-  l.i1_stride = opp_lo_align(I * sizeof(int));
-  l.i4_stride = opp_lo_align(I * 4 * sizeof(int));
-  l.d4_stride = opp_lo_align(I * 4 * sizeof(double));
+  l.pose_stride = opp_ws_align(I * 48 * sizeof(double));
+  l.i1_stride = opp_ws_align(I * sizeof(int));
+  l.i4_stride = opp_ws_align(I * 4 * sizeof(int));
+  l.d4_stride = opp_ws_align(I * 4 * sizeof(double));
   l.ctl_stride = 64;
   size_t off = 0;
   l.hyp = off, off += B * l.pose_stride;
@@ -59,9 +59,9 @@ OPP_BHD size_t opp_lo_batch_layout(int iterations, int n_samples, int n_total, O
   l.cand_ls = off, off += B * l.d4_stride;
   l.cand_pose = off, off += B * l.pose_stride;
   l.cand_taken = off, off += B * l.i4_stride;
-  l.ctl = off, off += opp_lo_align(B * l.ctl_stride);
-  l.lo_pts = off, off += opp_lo_align((size_t)OPP_LO_GRID * OPP_LO_PTS_ROW * n * sizeof(double));
-  l.fin_pts = off, off += opp_lo_align((size_t)OPP_LO_FIN_ROW * n * sizeof(double));
+  l.ctl = off, off += opp_ws_align(B * l.ctl_stride);
+  l.lo_pts = off, off += opp_ws_align((size_t)OPP_LO_GRID * OPP_LO_PTS_ROW * n * sizeof(double));
+  l.fin_pts = off, off += opp_ws_align((size_t)OPP_LO_FIN_ROW * n * sizeof(double));
   l.bytes = off;
   if (L) *L = l;
   return off;

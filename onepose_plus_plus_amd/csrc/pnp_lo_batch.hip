@@ -6,7 +6,7 @@
 // sizes n_b are known on the device only, so the one thing opp_pnp_loransac decides on the host from n_points -- n < 3 is the
 // failure -- is decided per sample in the kernels (opp_lo_mode, pnp_lo_batch.h), and a workgroup whose sample does not use a
 // kernel returns at once.  Each sample reads its own K4 and seed from device arrays and owns an `iterations`-sized slab of
-// every array of LoBuffers that scales with the trials, and a ctl of its own; its LO points start kLoGrid * 13 * offsets[b]
+// every array of LoBuffers that scales with the trials, and a ctl of its own; its LO points start OPP_LO_GRID * 13 * offsets[b]
 // doubles into one array, its final-stage points 21 * offsets[b] doubles into another (opp_lo_batch_layout).  Offsets that do
 // not describe a segment of [0, n_total] make an empty sample (opp_pnp_extent): nothing is read or written outside the
 // caller's arrays.
@@ -18,19 +18,16 @@
 //   grid (ceil(trials / 256), B)  loransac_batch_hypotheses_kernel
 //   grid (trials, B) x 256        loransac_batch_score_kernel
 //   grid (B)                      loransac_batch_candidates_kernel
-//   grid (kLoGrid, B) x 64        loransac_batch_optimise_kernel
+//   grid (OPP_LO_GRID, B) x 64        loransac_batch_optimise_kernel
 //   grid (B)                      loransac_batch_final_kernel
 //
 // Per sample the result is that of opp_pnp_loransac on its slice, bit for bit (tests/test_loransac_batch_gpu.py).  Every loop
 // has a fixed bound, no workgroup waits on another, and all arrays live in LDS or in the workspace.
 #include "opp_common.h"
-#include "pnp_lo_batch.h"
+#include "pnp_args.h"
 #include "pnp_lo_body.h"
 
 namespace {
-
-static_assert(kLoGrid == OPP_LO_GRID, "pnp_lo_batch.h lays out kLoGrid LO regions per sample");
-static_assert(OPP_LO_FIN_ROW == 5 + OPP_LM_ROW, "pnp_lo_batch.h lays out X, uv and a refinement row per match");
 
 struct LoBatch {
   const float* p2;
@@ -68,50 +65,12 @@ __device__ __forceinline__ LoSample lo_load_sample(const LoBatch& a, int b) {
   return s;
 }
 
-// sample b's buffers: its slabs, and the regions of the point arrays that follow its first match
-__device__ __forceinline__ LoBuffers lo_sample_buffers(const LoBatch& a, int b, int first) {
-  const OppLoBatchLayout& L = a.L;
-  const size_t sb = (size_t)b;
-  LoBuffers r;
-  r.hyp = (double*)(a.ws + L.hyp + sb * L.pose_stride);
-  r.nmod = (int*)(a.ws + L.nmod + sb * L.i1_stride);
-  r.cnt = (int*)(a.ws + L.cnt + sb * L.i4_stride);
-  r.sum = (double*)(a.ws + L.sum + sb * L.d4_stride);
-  r.cand_idx = (int*)(a.ws + L.cand_idx + sb * L.i4_stride);
-  r.cand_rc = (int*)(a.ws + L.cand_rc + sb * L.i4_stride);
-  r.cand_rs = (double*)(a.ws + L.cand_rs + sb * L.d4_stride);
-  r.cand_lc = (int*)(a.ws + L.cand_lc + sb * L.i4_stride);
-  r.cand_ls = (double*)(a.ws + L.cand_ls + sb * L.d4_stride);
-  r.cand_pose = (double*)(a.ws + L.cand_pose + sb * L.pose_stride);
-  r.cand_taken = (int*)(a.ws + L.cand_taken + sb * L.i4_stride);
-  r.ctl = (int*)(a.ws + L.ctl + sb * L.ctl_stride);
-  r.lo_pts = (double*)(a.ws + L.lo_pts) + (size_t)kLoGrid * OPP_LO_PTS_ROW * (size_t)first;
-  r.fin_pts = (double*)(a.ws + L.fin_pts) + (size_t)OPP_LO_FIN_ROW * (size_t)first;
-  return r;
-}
-
-__device__ __forceinline__ OppLoRecord lo_no_record() {
-  OppLoRecord rec;
-  rec.samples = nullptr;
-  rec.counts = nullptr;
-  rec.sums = nullptr;
-  rec.models = nullptr;
-  rec.n_cand = nullptr;
-  rec.cand_idx = nullptr;
-  rec.cand_cnt = nullptr;
-  rec.cand_sum = nullptr;
-  rec.cand_taken = nullptr;
-  rec.ransac_pose = nullptr;
-  rec.lm_iters = nullptr;
-  return rec;
-}
-
 // second != 0: the second pass, bounded by the sample's ctl[1]
 __global__ __launch_bounds__(256) void loransac_batch_hypotheses_kernel(LoBatch a, int t0, int t1, int second) {
   const int b = blockIdx.y;
   const LoSample s = lo_load_sample(a, b);
   if (s.mode != OPP_LO_RUN) return;
-  const LoBuffers bf = lo_sample_buffers(a, b, s.first);
+  const LoBuffers bf = lo_buffers(a.ws, a.L, b, s.first);
   lo_hypotheses_body(a.p2 + (size_t)2 * s.first, a.p3 + (size_t)3 * s.first, s.prm, t0, t1, second ? bf.ctl + 1 : nullptr, bf.hyp, bf.nmod,
                      nullptr, blockIdx.x * 256 + threadIdx.x);
 }
@@ -120,9 +79,9 @@ __global__ __launch_bounds__(256) void loransac_batch_score_kernel(LoBatch a, in
   const int b = blockIdx.y;
   const LoSample s = lo_load_sample(a, b);
   if (s.mode != OPP_LO_RUN) return;
-  const LoBuffers bf = lo_sample_buffers(a, b, s.first);
+  const LoBuffers bf = lo_buffers(a.ws, a.L, b, s.first);
   lo_score_body(a.p2 + (size_t)2 * s.first, a.p3 + (size_t)3 * s.first, s.prm, t0, t1, second ? bf.ctl + 1 : nullptr, bf.hyp, bf.nmod, bf.cnt,
-                bf.sum, lo_no_record(), blockIdx.x);
+                bf.sum, OppLoRecord{}, blockIdx.x);
 }
 
 // one workgroup per sample.  skip_t1 >= 0: the second pass
@@ -130,7 +89,7 @@ __global__ __launch_bounds__(256) void loransac_batch_candidates_kernel(LoBatch 
   const int b = blockIdx.x;
   const LoSample s = lo_load_sample(a, b);
   if (s.mode != OPP_LO_RUN) return;
-  const LoBuffers bf = lo_sample_buffers(a, b, s.first);
+  const LoBuffers bf = lo_buffers(a.ws, a.L, b, s.first);
   lo_candidates_body(t1, skip_t1 >= 0 ? bf.ctl + 1 : nullptr, skip_t1, bf);
 }
 
@@ -141,7 +100,7 @@ __global__ __launch_bounds__(64) void loransac_batch_optimise_kernel(LoBatch a, 
   __shared__ LoParams s_prm;   // the body indexes K4 by thread: in LDS, not in registers (no scratch)
   if (threadIdx.x == 0) s_prm = s.prm;
   __syncthreads();
-  const LoBuffers bf = lo_sample_buffers(a, b, s.first);
+  const LoBuffers bf = lo_buffers(a.ws, a.L, b, s.first);
   lo_optimise_body(a.p2 + (size_t)2 * s.first, a.p3 + (size_t)3 * s.first, s_prm, skip_t1 >= 0 ? bf.ctl + 1 : nullptr, skip_t1, bf, blockIdx.x,
                    gridDim.x);
 }
@@ -155,9 +114,9 @@ __global__ __launch_bounds__(256) void loransac_batch_final_kernel(LoBatch a, in
   __shared__ LoParams s_prm;   // as in loransac_batch_optimise_kernel
   if (threadIdx.x == 0) s_prm = s.prm;
   __syncthreads();
-  const LoBuffers bf = lo_sample_buffers(a, b, s.first);
+  const LoBuffers bf = lo_buffers(a.ws, a.L, b, s.first);
   lo_final_body(a.p2 + (size_t)2 * s.first, a.p3 + (size_t)3 * s.first, s_prm, bound_pass ? 0 : (s.mode == OPP_LO_RUN ? 1 : 2), bf,
-                a.pose_out + (size_t)12 * b, a.mask + s.first, a.n_inl + b, a.ok + b, a.stop + b, lo_no_record());
+                a.pose_out + (size_t)12 * b, a.mask + s.first, a.n_inl + b, a.ok + b, a.stop + b, OppLoRecord{});
 }
 
 }  // namespace
@@ -171,13 +130,9 @@ extern "C" int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, co
                                       double min_inlier_ratio, double* pose_out, int* inlier_mask, int* n_inliers, int* ok, int* stop, void* ws,
                                       size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
-  OPP_CHECK_ARG((n_total == 0 || (pts2d && pts3d)) && n_total >= 0 && offsets && K4 && seeds && pose_out && inlier_mask && n_inliers &&
-                    ok && stop && ws,
-                "pnp_loransac_batch: null argument");
-  OPP_CHECK_ARG(n_samples >= 1 && n_samples <= 1024, "pnp_loransac_batch: n_samples must be in [1, 1024]");
-  OPP_CHECK_ARG(iterations > 0 && iterations <= (1 << 20) && reproj_error_px > 0 && min_trials >= 0 && min_inlier_ratio >= 0.0,
-                "pnp_loransac_batch: bad parameters");
-  OPP_CHECK_ARG(confidence > 0.0, "pnp_loransac_batch: confidence must be > 0 (>= 1: no early stop)");
+  OPP_TRY(opp_pnp_check_batch("pnp_loransac_batch", n_samples, offsets, seeds, stop));
+  OPP_TRY(opp_pnp_check_args("pnp_loransac_batch", pts2d, pts3d, n_total, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations,
+                             reproj_error_px, min_trials >= 0 && min_inlier_ratio >= 0.0, confidence));
   OPP_CHECK_ARG(ws_bytes >= opp_pnp_loransac_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_loransac_batch: workspace too small");
   LoBatch a;
   a.p2 = pts2d;
@@ -203,14 +158,14 @@ extern "C" int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, co
   hipLaunchKernelGGL(loransac_batch_hypotheses_kernel, dim3(opp_cdiv(t1, 256), n_samples), dim3(256), 0, stream, a, 0, t1, 0);
   hipLaunchKernelGGL(loransac_batch_score_kernel, dim3(t1, n_samples), dim3(256), 0, stream, a, 0, t1, 0);
   hipLaunchKernelGGL(loransac_batch_candidates_kernel, dim3(n_samples), dim3(256), 0, stream, a, t1, -1);
-  hipLaunchKernelGGL(loransac_batch_optimise_kernel, dim3(kLoGrid, n_samples), dim3(64), 0, stream, a, -1);
+  hipLaunchKernelGGL(loransac_batch_optimise_kernel, dim3(OPP_LO_GRID, n_samples), dim3(64), 0, stream, a, -1);
   if (t1 < iterations) {   // the trials up to each sample's bound after the first pass (read on the device; nothing runs past it)
     hipLaunchKernelGGL(loransac_batch_final_kernel, dim3(n_samples), dim3(256), 0, stream, a, 1);
     hipLaunchKernelGGL(loransac_batch_hypotheses_kernel, dim3(opp_cdiv(iterations - t1, 256), n_samples), dim3(256), 0, stream, a, t1,
                        iterations, 1);
     hipLaunchKernelGGL(loransac_batch_score_kernel, dim3(iterations - t1, n_samples), dim3(256), 0, stream, a, t1, iterations, 1);
     hipLaunchKernelGGL(loransac_batch_candidates_kernel, dim3(n_samples), dim3(256), 0, stream, a, iterations, t1);
-    hipLaunchKernelGGL(loransac_batch_optimise_kernel, dim3(kLoGrid, n_samples), dim3(64), 0, stream, a, t1);
+    hipLaunchKernelGGL(loransac_batch_optimise_kernel, dim3(OPP_LO_GRID, n_samples), dim3(64), 0, stream, a, t1);
   }
   hipLaunchKernelGGL(loransac_batch_final_kernel, dim3(n_samples), dim3(256), 0, stream, a, 0);
   OPP_CHECK_LAUNCH("pnp_loransac_batch kernels");

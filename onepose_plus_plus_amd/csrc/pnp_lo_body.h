@@ -2,15 +2,15 @@
 // (pnp_lo_batch.hip): each kernel of either file is a few lines that find their sample's pointers, LoParams and LoBuffers and
 // call one of these, so a sample of a batch runs the arithmetic of the single call, in the same order -- lane l sums the points
 // l, l + 64, ... and a butterfly follows; the candidate scan is chunked by lim * 4 / 256; inliers are compacted in point order.
-// Every loop has a fixed bound, no workgroup waits on another, all arrays live in LDS or in the workspace.  Device only.
+// Every loop has a fixed bound, no workgroup waits on another, all arrays live in LDS or in the workspace.  Device only, but for
+// lo_buffers, which the host of pnp_lo.hip calls too.
 #pragma once
+#include "pnp_lo_batch.h"
 #include "pnp_math.h"
 #include "pnp_sample.h"
 #include "../../include/opp_hip.h"
 
 namespace {
-
-constexpr int kLoGrid = 32;   // workgroups of the LO kernel per sample (each with its own 13 n doubles of workspace)
 
 struct LoParams {
   double K4[4];      // fx, fy, cx, cy (fy = fx for the reference's SIMPLE_PINHOLE camera)
@@ -34,9 +34,31 @@ struct LoBuffers {
   double* cand_pose;  // [iters * 4][12] pose after LO
   int* cand_taken;
   int* ctl;           // [0] number of candidates, [1] bound on the trials after the first pass
-  double* lo_pts;     // [kLoGrid][13 n]
+  double* lo_pts;     // [OPP_LO_GRID][13 n]
   double* fin_pts;    // [21 n]
 };
+
+// sample b's buffers in a workspace laid out by opp_lo_batch_layout: its slabs, and the regions of the point arrays that follow
+// its first match.  The single call is sample 0 of a batch of one
+__host__ __device__ __forceinline__ LoBuffers lo_buffers(char* ws, const OppLoBatchLayout& L, int b, int first) {
+  const size_t sb = (size_t)b;
+  LoBuffers r;
+  r.hyp = (double*)(ws + L.hyp + sb * L.pose_stride);
+  r.nmod = (int*)(ws + L.nmod + sb * L.i1_stride);
+  r.cnt = (int*)(ws + L.cnt + sb * L.i4_stride);
+  r.sum = (double*)(ws + L.sum + sb * L.d4_stride);
+  r.cand_idx = (int*)(ws + L.cand_idx + sb * L.i4_stride);
+  r.cand_rc = (int*)(ws + L.cand_rc + sb * L.i4_stride);
+  r.cand_rs = (double*)(ws + L.cand_rs + sb * L.d4_stride);
+  r.cand_lc = (int*)(ws + L.cand_lc + sb * L.i4_stride);
+  r.cand_ls = (double*)(ws + L.cand_ls + sb * L.d4_stride);
+  r.cand_pose = (double*)(ws + L.cand_pose + sb * L.pose_stride);
+  r.cand_taken = (int*)(ws + L.cand_taken + sb * L.i4_stride);
+  r.ctl = (int*)(ws + L.ctl + sb * L.ctl_stride);
+  r.lo_pts = (double*)(ws + L.lo_pts) + (size_t)OPP_LO_GRID * OPP_LO_PTS_ROW * (size_t)first;
+  r.fin_pts = (double*)(ws + L.fin_pts) + (size_t)OPP_LO_FIN_ROW * (size_t)first;
+  return r;
+}
 
 __device__ __forceinline__ void lo_load_pose(const double* src, OppPose& P) {
 #pragma unroll

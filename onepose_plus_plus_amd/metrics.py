@@ -125,22 +125,14 @@ def _batch_poses(data, configs, query_K, pnp_kwargs, batch_loransac=False):
     [0, B)), which the loop's `m_bids == bs` selection does not need.  The order is checked on the device and read back with the
     poses, so such ids pay for the batch pass AND the loop; a RuntimeWarning says so."""
     from . import pose
-    solver = pnp_kwargs.get("solver", "p3p")
-    if solver == "auto":
-        solver = "loransac" if configs["use_pycolmap_ransac"] else "epnp"
-    if solver not in ("p3p", "epnp", "loransac") or query_K.shape[0] > 1024:   # 1024: the batch passes' limit on B
+    options = dict(scale=configs["point_cloud_rescale"], **pnp_kwargs)
+    found = pose._batch_call(options, configs["use_pycolmap_ransac"], batch_loransac)
+    if found is None or query_K.shape[0] > 1024:   # 1024: the batch passes' limit on B
         return None
-    if solver == "loransac" and not batch_loransac:
-        return None
+    call, kw = found
     try:
-        if solver == "loransac":   # the reference's pycolmap branch: no `scale`; `refine_iters` is "p3p"'s
-            kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "scale", "refine_iters")}
-            return pose.loransac_PnP_batch(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
-                                           pnp_reprojection_error=configs["pnp_reprojection_error"], **kw)
-        kw = {k: v for k, v in pnp_kwargs.items() if k not in ("solver", "min_trials", "min_inlier_ratio")}   # the last two: "loransac" only
-        return pose.ransac_PnP_batch(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
-                                     scale=configs["point_cloud_rescale"],
-                                     pnp_reprojection_error=configs["pnp_reprojection_error"], solver=solver, **kw)
+        return call(query_K, data["mkpts_query_f"], data["mkpts_3d_db"], m_bids=data["m_bids"],
+                    pnp_reprojection_error=configs["pnp_reprojection_error"], **kw)
     except pose.BatchIdsError:
         warnings.warn("compute_query_pose_errors: m_bids is not non-decreasing in [0, B); the batch pass was discarded and the "
                       "poses are estimated per sample", RuntimeWarning, stacklevel=3)

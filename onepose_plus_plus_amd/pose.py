@@ -69,64 +69,111 @@ def _dev_f32(a, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
-_SOLVERS = {"p3p": 0, "epnp": 1}
+_SOLVERS = {"p3p": 0, "epnp": 1}                                   # the C calls' solver numbers
 _SOLVER_NAMES = ("p3p", "epnp", "loransac")
+_CONFIDENCE = {"p3p": 1.0, "epnp": 0.99, "loransac": 0.9999}        # confidence=None; 1.0: every hypothesis is evaluated
+# the options of `ransac_PnP` a solver has no use for, which its batch call therefore does not take
+_NOT_TAKEN = {"p3p": ("min_trials", "min_inlier_ratio"), "epnp": ("min_trials", "min_inlier_ratio"), "loransac": ("scale", "refine_iters")}
 
 
-def _bad_solver(solver, allowed):
-    return ValueError("solver must be one of %s, got %r" % (", ".join(repr(a) for a in allowed), solver))
+def _resolve_solver(solver, use_pycolmap_ransac=False, auto=True):
+    """the estimator's name; with `auto`, "auto" = what the reference would run.  Any other name raises ValueError"""
+    if auto and solver == "auto":
+        return "loransac" if use_pycolmap_ransac else "epnp"
+    if solver not in _SOLVER_NAMES:
+        allowed = _SOLVER_NAMES + (("auto",) if auto else ())
+        raise ValueError("solver must be one of %s, got %r" % (", ".join(repr(a) for a in allowed), solver))
+    return solver
 
 
-def _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, confidence, min_trials, min_inlier_ratio,
-              simple_pinhole, record):
-    """`opp_pnp_loransac` -> the dict of `ransac_PnP_ex`"""
+def _confidence(solver, confidence):
+    return _CONFIDENCE[solver] if confidence is None else confidence
+
+
+def _device(pts_2d, device):
+    if device is not None:
+        return device
+    return pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+
+
+def _homo(pose):
+    """[3,4] -> [4,4], [B,3,4] -> [B,4,4]"""
+    out = np.zeros(pose.shape[:-2] + (4, 4))
+    out[..., :3, :] = pose
+    out[..., 3, 3] = 1.0
+    return out
+
+
+def _failure():
+    """the reference's `cv2.error` branch"""
+    return np.eye(4)[:3], np.eye(4), np.array([]).astype(bool), False
+
+
+def _single(K, pts_2d, pts_3d, device, n_cnt, ws_bytes, call, simple_pinhole=False, record_bufs=None):
+    """One single-sample C call and its device-to-host copy.  cnt = n_inliers, ok(, stop(, the caller's)) is `n_cnt` ints;
+    ws_bytes(lib, n) sizes the workspace; record_bufs(device) -> dict of the caller's extra device tensors;
+    call(lib, p2, p3, n, K4, out, mask, cnt, bufs, ws, nbytes, stream) -- pointers but for n, bufs and nbytes -- -> (return code, name).
+    -> (dict(pose [3,4], state, inliers [k] int32(, stop)), cnt on the host as float64, bufs)"""
     lib = _lib.load()
-    if device is None:
-        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = _device(pts_2d, device)
     Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
     Kn = Kn.astype(np.float64)
     K4 = (ctypes.c_double * 4)(Kn[0, 0], Kn[0, 0] if simple_pinhole else Kn[1, 1], Kn[0, 2], Kn[1, 2])
     p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
     p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
     n = int(p2.shape[0])
-    iterations = int(iterations)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
         out = torch.empty(12, dtype=torch.float64, device=device)
         mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        cnt = torch.zeros(5, dtype=torch.int32, device=device)          # n_inliers, ok, stop, n_cand, lm_iters
-        rec, bufs = None, {}
-        if record:
-            i32, f64 = torch.int32, torch.float64
-            bufs = {"samples": torch.full((iterations, 3), -1, dtype=i32, device=device),
-                    "counts": torch.full((iterations, 4), -1, dtype=i32, device=device),
-                    "sums": torch.zeros((iterations, 4), dtype=f64, device=device),
-                    "models": torch.zeros((iterations, 4, 12), dtype=f64, device=device),
-                    "cand_idx": torch.full((iterations * 4,), -1, dtype=i32, device=device),
-                    "cand_cnt": torch.full((iterations * 4,), -1, dtype=i32, device=device),
-                    "cand_sum": torch.zeros((iterations * 4,), dtype=f64, device=device),
-                    "cand_taken": torch.zeros((iterations * 4,), dtype=i32, device=device),
-                    "ransac_pose": torch.zeros(12, dtype=f64, device=device)}
-            rec = _lib.OppLoRecord(n_cand=cnt.data_ptr() + 12, lm_iters=cnt.data_ptr() + 16, **{k: v.data_ptr() for k, v in bufs.items()})
-        nbytes = lib.opp_pnp_loransac_workspace_bytes(iterations, n)
+        cnt = torch.zeros(n_cnt, dtype=torch.int32, device=device)
+        bufs = record_bufs(device) if record_bufs else {}
+        nbytes = ws_bytes(lib, n)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.opp_pnp_loransac(p2.data_ptr(), p3.data_ptr(), n, K4, float(pnp_reprojection_error), iterations,
-                                        int(seed) & 0xFFFFFFFF, float(confidence), int(min_trials), float(min_inlier_ratio),
-                                        out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4, cnt.data_ptr() + 8,
-                                        ctypes.addressof(rec) if rec is not None else None, ws.data_ptr(), nbytes, stream),
-                   "opp_pnp_loransac")
+        _lib.check(*call(lib, p2.data_ptr(), p3.data_ptr(), n, K4, out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), bufs, ws.data_ptr(),
+                         nbytes, stream))
         host = torch.cat([out, cnt.double()]).cpu().numpy()              # one D2H copy
-        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0), "stop": int(host[14])}
+        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0)}
+        if n_cnt > 2:
+            res["stop"] = int(host[14])
         res["inliers"] = torch.nonzero(mask[:n]).to(torch.int32).cpu().numpy().reshape(-1) if res["state"] else \
             np.zeros(0, np.int32)
-        if record:
-            nc = int(host[15])
-            res["lm_iters"] = int(host[16])
-            for k in ("samples", "counts", "sums", "models"):
-                res[k] = bufs[k].cpu().numpy()
-            for k in ("cand_idx", "cand_cnt", "cand_sum", "cand_taken"):
-                res[k] = bufs[k][:nc].cpu().numpy()
-            res["ransac_pose"] = bufs["ransac_pose"].cpu().numpy().reshape(3, 4)
+    return res, host[12:], bufs
+
+
+def _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, confidence, min_trials, min_inlier_ratio,
+              simple_pinhole, record):
+    """`opp_pnp_loransac` -> the dict of `ransac_PnP_ex`"""
+    iterations = int(iterations)
+
+    def record_bufs(device):
+        i32, f64 = torch.int32, torch.float64
+        return {"samples": torch.full((iterations, 3), -1, dtype=i32, device=device),
+                "counts": torch.full((iterations, 4), -1, dtype=i32, device=device),
+                "sums": torch.zeros((iterations, 4), dtype=f64, device=device),
+                "models": torch.zeros((iterations, 4, 12), dtype=f64, device=device),
+                "cand_idx": torch.full((iterations * 4,), -1, dtype=i32, device=device),
+                "cand_cnt": torch.full((iterations * 4,), -1, dtype=i32, device=device),
+                "cand_sum": torch.zeros((iterations * 4,), dtype=f64, device=device),
+                "cand_taken": torch.zeros((iterations * 4,), dtype=i32, device=device),
+                "ransac_pose": torch.zeros(12, dtype=f64, device=device)}
+
+    def call(lib, p2, p3, n, K4, out, mask, cnt, bufs, ws, nbytes, stream):
+        rec = _lib.OppLoRecord(n_cand=cnt + 12, lm_iters=cnt + 16, **{k: v.data_ptr() for k, v in bufs.items()}) if record else None
+        return lib.opp_pnp_loransac(p2, p3, n, K4, float(pnp_reprojection_error), iterations, int(seed) & 0xFFFFFFFF, float(confidence),
+                                    int(min_trials), float(min_inlier_ratio), out, mask, cnt, cnt + 4, cnt + 8,
+                                    ctypes.addressof(rec) if record else None, ws, nbytes, stream), "opp_pnp_loransac"
+
+    res, cnt, bufs = _single(K, pts_2d, pts_3d, device, 5, lambda lib, n: lib.opp_pnp_loransac_workspace_bytes(iterations, n), call,
+                             simple_pinhole, record_bufs if record else None)          # cnt: n_inliers, ok, stop, n_cand, lm_iters
+    if record:
+        nc = int(cnt[3])
+        res["lm_iters"] = int(cnt[4])
+        for k in ("samples", "counts", "sums", "models"):
+            res[k] = bufs[k].cpu().numpy()
+        for k in ("cand_idx", "cand_cnt", "cand_sum", "cand_taken"):
+            res[k] = bufs[k][:nc].cpu().numpy()
+        res["ransac_pose"] = bufs["ransac_pose"].cpu().numpy().reshape(3, 4)
     return res
 
 
@@ -141,45 +188,27 @@ def ransac_PnP_ex(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, iteratio
     every model that beats all earlier ones), its supports after local optimisation `cand_cnt` / `cand_sum`, `cand_taken` (the
     candidates that became the best in the sequential loop; the last one is the result), `ransac_pose` [3,4] before the
     refinement and `lm_iters`."""
-    if solver not in _SOLVER_NAMES:
-        raise _bad_solver(solver, _SOLVER_NAMES)
+    solver = _resolve_solver(solver, auto=False)
+    confidence = _confidence(solver, confidence)
     if solver == "loransac":
-        return _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, 0.9999 if confidence is None else confidence,
-                         min_trials, min_inlier_ratio, simple_pinhole, record)
-    if confidence is None:
-        confidence = 0.99 if solver == "epnp" else 1.0
-    lib = _lib.load()
-    if device is None:
-        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
-    Kn = Kn.astype(np.float64)
-    K4 = (ctypes.c_double * 4)(Kn[0, 0], Kn[1, 1], Kn[0, 2], Kn[1, 2])
-    p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
-    p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
-    n = int(p2.shape[0])
+        return _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, device, confidence, min_trials, min_inlier_ratio,
+                         simple_pinhole, record)
     iterations = int(iterations)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        out = torch.empty(12, dtype=torch.float64, device=device)
-        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        cnt = torch.zeros(3, dtype=torch.int32, device=device)          # n_inliers, ok, stop
-        samples = torch.full((iterations, 5), -1, dtype=torch.int32, device=device) if record else None
-        scores = torch.full((iterations,), -1, dtype=torch.int32, device=device) if record else None
-        nbytes = lib.opp_pnp_ex_workspace_bytes(iterations, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.opp_pnp_ransac_ex(p2.data_ptr(), p3.data_ptr(), n, K4, float(pnp_reprojection_error), float(scale),
-                                         iterations, int(seed) & 0xFFFFFFFF, int(refine_iters), _SOLVERS[solver], float(confidence),
-                                         out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4, cnt.data_ptr() + 8,
-                                         samples.data_ptr() if record else None, scores.data_ptr() if record else None,
-                                         ws.data_ptr(), nbytes, stream),
-                   "opp_pnp_ransac_ex")
-        host = torch.cat([out, cnt.double()]).cpu().numpy()              # one D2H copy
-        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0), "stop": int(host[14])}
-        res["inliers"] = torch.nonzero(mask[:n]).to(torch.int32).cpu().numpy().reshape(-1) if res["state"] else \
-            np.zeros(0, np.int32)
-        if record:
-            res["samples"] = samples.cpu().numpy()
-            res["scores"] = scores.cpu().numpy()
+
+    def record_bufs(device):
+        return {"samples": torch.full((iterations, 5), -1, dtype=torch.int32, device=device),
+                "scores": torch.full((iterations,), -1, dtype=torch.int32, device=device)}
+
+    def call(lib, p2, p3, n, K4, out, mask, cnt, bufs, ws, nbytes, stream):
+        return lib.opp_pnp_ransac_ex(p2, p3, n, K4, float(pnp_reprojection_error), float(scale), iterations, int(seed) & 0xFFFFFFFF,
+                                     int(refine_iters), _SOLVERS[solver], float(confidence), out, mask, cnt, cnt + 4, cnt + 8,
+                                     bufs["samples"].data_ptr() if record else None, bufs["scores"].data_ptr() if record else None,
+                                     ws, nbytes, stream), "opp_pnp_ransac_ex"
+
+    res, _, bufs = _single(K, pts_2d, pts_3d, device, 3, lambda lib, n: lib.opp_pnp_ex_workspace_bytes(iterations, n), call,
+                           record_bufs=record_bufs if record else None)                # cnt: n_inliers, ok, stop
+    for k in bufs:
+        res[k] = bufs[k].cpu().numpy()
     return res
 
 
@@ -187,24 +216,27 @@ class BatchIdsError(ValueError):
     """`ransac_PnP_batch`: the batch ids are not non-decreasing, or not all in [0, B)"""
 
 
-def _batch_solver(solver, use_pycolmap_ransac):
-    """the solver `ransac_PnP_batch` runs ("p3p" / "epnp"); "loransac", named or resolved from "auto", is `loransac_PnP_batch`'s"""
-    if solver == "auto":
-        solver = "loransac" if use_pycolmap_ransac else "epnp"
-    elif solver not in _SOLVER_NAMES:
-        raise _bad_solver(solver, _SOLVER_NAMES + ("auto",))
+def _batch_call(options, use_pycolmap_ransac=False, batch_loransac=True):
+    """options: keyword arguments as `ransac_PnP` takes them (solver, scale, seed, ...) -> (the batch call that runs that solver, the
+    options it takes), or None where no batch call is to run: a solver name that `ransac_PnP` refuses, or "loransac" (named, or what
+    "auto" resolves to) without `batch_loransac`"""
+    try:
+        solver = _resolve_solver(options.get("solver", "p3p"), use_pycolmap_ransac)
+    except ValueError:
+        return None
+    if solver == "loransac" and not batch_loransac:
+        return None
+    kw = {k: v for k, v in options.items() if k not in ("solver",) + _NOT_TAKEN[solver]}
     if solver == "loransac":
-        raise NotImplementedError('ransac_PnP_batch runs "p3p" and "epnp"; LO-RANSAC has a batch pass of its own, loransac_PnP_batch '
-                                  '(or call ransac_PnP(solver="loransac") / ransac_PnP_ex for each sample)')
-    return solver
+        return loransac_PnP_batch, kw
+    return ransac_PnP_batch, dict(kw, solver=solver)
 
 
 def _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device):
     """the argument checks and host-side inputs the batch calls share -> (device, K [B,3,3] float64, seeds [B], p2, p3)"""
     if (m_bids is None) == (offsets is None):
         raise ValueError("%s: give exactly one of m_bids and offsets" % name)
-    if device is None:
-        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    device = _device(pts_2d, device)
     Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
     Kn = Kn.astype(np.float64).reshape(-1, 3, 3)
     B = int(Kn.shape[0])
@@ -250,7 +282,6 @@ def _batch_result(name, out, cnt, off, mask, B, n):
     state = host[13 * B:14 * B] != 0
     stop = host[14 * B:15 * B].astype(np.int64)
     off_h = host[15 * B + 1:].astype(np.int64)
-    pose_homo = np.concatenate([pose, np.broadcast_to(np.array([[[0.0, 0.0, 0.0, 1.0]]]), (B, 1, 4))], axis=1)
     inliers = []
     for b in range(B):
         lo, hi = int(off_h[b]), int(off_h[b + 1])
@@ -258,7 +289,31 @@ def _batch_result(name, out, cnt, off, mask, B, n):
             inliers.append(np.nonzero(mask_h[lo:hi])[0].astype(np.int32).reshape(-1, 1))
         else:
             inliers.append(np.array([]).astype(bool))
-    return {"pose": pose, "pose_homo": pose_homo, "state": state, "stop": stop, "inliers": inliers, "pose_dev": out}
+    return {"pose": pose, "pose_homo": _homo(pose), "state": state, "stop": stop, "inliers": inliers, "pose_dev": out}
+
+
+def _batch_run(name, device, Kn, fy, seeds, p2, p3, m_bids, offsets, chunk, ws_bytes, call):
+    """The device buffers of a batch call, its C calls over `chunk` samples at a time through one workspace (ws_bytes(lib, n) sizes
+    it) and `_batch_result`.  Offsets are absolute, so a chunk is the same call further on:
+    call(lib, p2, p3, off, nb, n, K4, seeds, out, mask, n_inl, ok, stop, ws, nbytes, stream) -- pointers but for nb, n and nbytes,
+    those of the per-sample arrays at the chunk's first sample -- -> (return code, name)"""
+    lib = _lib.load()
+    B, n = int(Kn.shape[0]), int(p2.shape[0])
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream(device).cuda_stream
+        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], fy, Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
+        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
+        off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
+        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
+        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
+        nbytes = ws_bytes(lib, n)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        for b0 in range(0, B, chunk):
+            _lib.check(*call(lib, p2.data_ptr(), p3.data_ptr(), off.data_ptr() + 4 * b0, min(chunk, B - b0), n, K4.data_ptr() + 32 * b0,
+                             seeds_d.data_ptr() + 4 * b0, out.data_ptr() + 96 * b0, mask.data_ptr(), cnt.data_ptr() + 4 * b0,
+                             cnt.data_ptr() + 4 * (B + b0), cnt.data_ptr() + 4 * (2 * B + b0), ws.data_ptr(), nbytes, stream))
+        return _batch_result(name, out, cnt, off, mask, B, n)
 
 
 def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, scale=1, pnp_reprojection_error=5,
@@ -274,29 +329,21 @@ def ransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=No
     the sample (an empty bool array where state is False), pose_dev: the [B,3,4] float64 CUDA tensor.  Two device-to-host copies
     whatever B is (poses + counts + offsets, and the mask); ids that break the contract raise ValueError after the first."""
     name = "ransac_PnP_batch"
-    solver = _batch_solver(solver, use_pycolmap_ransac)
+    solver = _resolve_solver(solver, use_pycolmap_ransac)
+    if solver == "loransac":
+        raise NotImplementedError('ransac_PnP_batch runs "p3p" and "epnp"; LO-RANSAC has a batch pass of its own, loransac_PnP_batch '
+                                  '(or call ransac_PnP(solver="loransac") / ransac_PnP_ex for each sample)')
     device, Kn, seeds, p2, p3 = _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device)
-    if confidence is None:
-        confidence = 0.99 if solver == "epnp" else 1.0
-    lib = _lib.load()
-    B, n = int(Kn.shape[0]), int(p2.shape[0])
-    iterations = int(iterations)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], Kn[:, 1, 1], Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
-        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
-        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
-        off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
-        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
-        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        nbytes = lib.opp_pnp_batch_workspace_bytes(iterations, B, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.opp_pnp_ransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr(), B, n, K4.data_ptr(), seeds_d.data_ptr(),
-                                            float(pnp_reprojection_error), float(scale), iterations, int(refine_iters),
-                                            _SOLVERS[solver], float(confidence), out.data_ptr(), mask.data_ptr(), cnt.data_ptr(),
-                                            cnt.data_ptr() + 4 * B, cnt.data_ptr() + 8 * B, ws.data_ptr(), nbytes, stream),
-                   "opp_pnp_ransac_batch")
-        return _batch_result(name, out, cnt, off, mask, B, n)
+    confidence, iterations = _confidence(solver, confidence), int(iterations)
+
+    def call(lib, p2, p3, off, nb, n, K4, seeds, out, mask, n_inl, ok, stop, ws, nbytes, stream):
+        return lib.opp_pnp_ransac_batch(p2, p3, off, nb, n, K4, seeds, float(pnp_reprojection_error), float(scale), iterations,
+                                        int(refine_iters), _SOLVERS[solver], float(confidence), out, mask, n_inl, ok, stop, ws, nbytes,
+                                        stream), "opp_pnp_ransac_batch"
+
+    B = int(Kn.shape[0])
+    return _batch_run(name, device, Kn, Kn[:, 1, 1], seeds, p2, p3, m_bids, offsets, B,
+                      lambda lib, n: lib.opp_pnp_batch_workspace_bytes(iterations, B, n), call)
 
 
 def loransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=None, pnp_reprojection_error=5, iterations=10000,
@@ -318,29 +365,16 @@ def loransac_PnP_batch(K, pts_2d, pts_3d, m_bids=None, offsets=None, batch_size=
         raise ValueError("%s: focal lengths must be positive" % name)
     if int(max_batch) < 1:
         raise ValueError("%s: max_batch must be at least 1, got %d" % (name, int(max_batch)))
-    if confidence is None:
-        confidence = 0.9999
-    lib = _lib.load()
-    B, n = int(Kn.shape[0]), int(p2.shape[0])
-    iterations, chunk = int(iterations), min(int(max_batch), B)
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], fy, Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
-        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
-        cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
-        off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
-        out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)
-        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        nbytes = lib.opp_pnp_loransac_batch_workspace_bytes(iterations, chunk, n)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        for b0 in range(0, B, chunk):                                    # offsets are absolute: a chunk is the same call further on
-            _lib.check(lib.opp_pnp_loransac_batch(p2.data_ptr(), p3.data_ptr(), off.data_ptr() + 4 * b0, min(chunk, B - b0), n,
-                                                  K4.data_ptr() + 32 * b0, seeds_d.data_ptr() + 4 * b0, float(pnp_reprojection_error),
-                                                  iterations, float(confidence), int(min_trials), float(min_inlier_ratio),
-                                                  out.data_ptr() + 96 * b0, mask.data_ptr(), cnt.data_ptr() + 4 * b0,
-                                                  cnt.data_ptr() + 4 * (B + b0), cnt.data_ptr() + 4 * (2 * B + b0), ws.data_ptr(), nbytes,
-                                                  stream), "opp_pnp_loransac_batch")
-        return _batch_result(name, out, cnt, off, mask, B, n)
+    confidence, iterations = _confidence("loransac", confidence), int(iterations)
+    chunk = min(int(max_batch), int(Kn.shape[0]))
+
+    def call(lib, p2, p3, off, nb, n, K4, seeds, out, mask, n_inl, ok, stop, ws, nbytes, stream):
+        return lib.opp_pnp_loransac_batch(p2, p3, off, nb, n, K4, seeds, float(pnp_reprojection_error), iterations, float(confidence),
+                                          int(min_trials), float(min_inlier_ratio), out, mask, n_inl, ok, stop, ws, nbytes,
+                                          stream), "opp_pnp_loransac_batch"
+
+    return _batch_run(name, device, Kn, fy, seeds, p2, p3, m_bids, offsets, chunk,
+                      lambda lib, n: lib.opp_pnp_loransac_batch_workspace_bytes(iterations, chunk, n), call)
 
 
 def ransac_PnP(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, img_hw=None, use_pycolmap_ransac=False,
@@ -351,43 +385,16 @@ def ransac_PnP(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, img_hw=None
     "epnp" otherwise.  With "p3p" / "epnp" `use_pycolmap_ransac` is ignored; `img_hw` is accepted and unused, as in the reference.
     confidence: None = the solver's default (off for "p3p", 0.99 for "epnp", 0.9999 for "loransac"); refine_iters: "p3p" only;
     min_trials / min_inlier_ratio: "loransac" only, which also leaves `scale` unapplied (the reference's pycolmap branch does)."""
-    if solver == "auto":
-        solver = "loransac" if use_pycolmap_ransac else "epnp"
-    elif solver not in _SOLVER_NAMES:
-        raise _bad_solver(solver, _SOLVER_NAMES + ("auto",))
+    solver = _resolve_solver(solver, use_pycolmap_ransac)
     if solver != "p3p" or confidence is not None:
         r = ransac_PnP_ex(K, pts_2d, pts_3d, scale, pnp_reprojection_error, iterations, refine_iters, seed, device, solver,
                           confidence, min_trials=min_trials, min_inlier_ratio=min_inlier_ratio)
-        if not r["state"]:
-            return np.eye(4)[:3], np.eye(4), np.array([]).astype(bool), False
-        pose = r["pose"]
-        pose_homo = np.concatenate([pose, np.array([[0.0, 0.0, 0.0, 1.0]])], axis=0)
-        return pose, pose_homo, r["inliers"].reshape(-1, 1), True
-    lib = _lib.load()
-    if device is None:
-        device = pts_2d.device if torch.is_tensor(pts_2d) and pts_2d.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
-    Kn = Kn.astype(np.float64)
-    K4 = (ctypes.c_double * 4)(Kn[0, 0], Kn[1, 1], Kn[0, 2], Kn[1, 2])
-    p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
-    p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
-    n = int(p2.shape[0])
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device).cuda_stream
-        out = torch.empty(12, dtype=torch.float64, device=device)
-        mask = torch.empty(max(n, 1), dtype=torch.int32, device=device)
-        cnt = torch.zeros(2, dtype=torch.int32, device=device)          # n_inliers, ok
-        nbytes = lib.opp_pnp_workspace_bytes(int(iterations))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _lib.check(lib.opp_pnp_ransac(p2.data_ptr(), p3.data_ptr(), n, K4, float(pnp_reprojection_error), float(scale),
-                                      int(iterations), int(seed) & 0xFFFFFFFF, int(refine_iters), out.data_ptr(),
-                                      mask.data_ptr(), cnt.data_ptr(), cnt.data_ptr() + 4, ws.data_ptr(), nbytes, stream),
-                   "opp_pnp_ransac")
-        host = torch.cat([out, cnt.double()]).cpu().numpy()              # one D2H copy
-    pose = host[:12].reshape(3, 4).copy()
-    state = bool(host[13] != 0)
-    pose_homo = np.concatenate([pose, np.array([[0.0, 0.0, 0.0, 1.0]])], axis=0)
-    if not state:
-        return np.eye(4)[:3], np.eye(4), np.array([]).astype(bool), False
-    inliers = torch.nonzero(mask[:n]).to(torch.int32).cpu().numpy().reshape(-1, 1)   # OpenCV returns [n_inl, 1] indices
-    return pose, pose_homo, inliers, True
+    else:                                        # every hypothesis, no stop stage: `opp_pnp_ransac`, one launch fewer
+        def call(lib, p2, p3, n, K4, out, mask, cnt, bufs, ws, nbytes, stream):
+            return lib.opp_pnp_ransac(p2, p3, n, K4, float(pnp_reprojection_error), float(scale), int(iterations), int(seed) & 0xFFFFFFFF,
+                                      int(refine_iters), out, mask, cnt, cnt + 4, ws, nbytes, stream), "opp_pnp_ransac"
+
+        r, _, _ = _single(K, pts_2d, pts_3d, device, 2, lambda lib, n: lib.opp_pnp_workspace_bytes(int(iterations)), call)
+    if not r["state"]:
+        return _failure()
+    return r["pose"], _homo(r["pose"]), r["inliers"].reshape(-1, 1), True        # OpenCV returns [n_inl, 1] indices

@@ -22,7 +22,7 @@ STRIDES = ("pose_stride", "i1_stride", "i4_stride", "d4_stride", "ctl_stride")
 SLABS = {"hyp": ("pose_stride", 384), "nmod": ("i1_stride", 4), "cnt": ("i4_stride", 16), "sum": ("d4_stride", 32),
          "cand_idx": ("i4_stride", 16), "cand_rc": ("i4_stride", 16), "cand_rs": ("d4_stride", 32), "cand_lc": ("i4_stride", 16),
          "cand_ls": ("d4_stride", 32), "cand_pose": ("pose_stride", 384), "cand_taken": ("i4_stride", 16)}
-LO_ROW, FIN_ROW = 32 * 13 * 8, 21 * 8          # bytes per match: kLoGrid workgroups of 13 doubles; X, uv and a 16-double LM row
+LO_ROW, FIN_ROW = 32 * 13 * 8, 21 * 8          # bytes per match: OPP_LO_GRID workgroups of 13 doubles; X, uv and a 16-double LM row
 
 
 @pytest.fixture(scope="module")
@@ -38,7 +38,7 @@ def lib(tmp_path_factory):
 
 
 def test_mode_is_the_host_decision_of_the_single_call(lib):
-    # opp_pnp_loransac (csrc/pnp_lo.hip): `if (n_points < 3)` launches the final kernel in mode 2 alone
+    # opp_pnp_loransac (csrc/pnp_lo.hip) asks it too: FAIL launches the final kernel in mode 2 alone
     assert [lib.t_lo_mode(n) for n in range(6)] == [FAIL, FAIL, FAIL, RUN, RUN, RUN]
     assert lib.t_lo_mode(100000) == RUN and lib.t_lo_mode(2 ** 31 - 1) == RUN
 
@@ -104,6 +104,20 @@ def test_layout_of_invalid_offsets_stays_inside(lib):
     lo0, lo1, f0, f1 = _regions(lib, 100, 3, 9, 0, 9)                                                     # the whole array
     assert lo1 <= L["fin_pts"] and f1 <= L["bytes"]
     assert _layout(lib, 0, 0, 0) == _layout(lib, 1, 1, 1)                                                  # never a zero-sized workspace
+
+
+@pytest.mark.parametrize("iterations", [1, 63, 64, 2000, 10000])
+@pytest.mark.parametrize("n", [0, 1, 4, 5, 6, 300])
+def test_single_call_workspace_is_the_batch_layout_of_one_sample(lib, iterations, n):
+    # opp_pnp_loransac_workspace_bytes as pnp_lo.hip wrote it out before it used the layout: fourteen 256-aligned blocks
+    I, nn = max(iterations, 1), max(n, 1)
+    blocks = [I * 48 * 8, I * 4, I * 16, I * 32, I * 16, I * 16, I * 32, I * 16, I * 32, I * 48 * 8, I * 16, 64, 32 * 13 * nn * 8, 21 * nn * 8]
+    L = _layout(lib, iterations, 1, n)
+    assert L["bytes"] == sum((x + 255) // 256 * 256 for x in blocks)
+    off = 0
+    for name, x in zip(ARRAYS, blocks):                     # and in the same order
+        assert L[name] == off, name
+        off += (x + 255) // 256 * 256
 
 
 def test_workspace_grows_with_every_argument(lib):

@@ -83,7 +83,7 @@ def test_extent_of_unvalidated_offsets(lib):
 
 
 def _host_decisions(solver, n):
-    """what opp_pnp_ransac_ex decides on the host from n_points (csrc/pnp.hip), restated: (mode, m)"""
+    """what opp_pnp_ransac_ex decided on the host from n_points before it read opp_pnp_mode, restated: (mode, m)"""
     sample = n >= 4 if solver == 0 else (n == 4 or n >= 6)
     if solver == 0:
         return (P3P_RANSAC if sample else FAIL), 4          # pnp_stop_kernel(..., 4, ...) / prm.iters = 0
@@ -106,6 +106,71 @@ def test_mode_table(lib, solver):
     assert lib.t_mode(1, 4, ctypes.byref(m)) == P3P_RANSAC and m.value == 4
     assert lib.t_mode(1, 6, ctypes.byref(m)) == EPNP_RANSAC and m.value == 5
     assert lib.t_mode(solver, 100000, ctypes.byref(m)) == (P3P_RANSAC if solver == 0 else EPNP_RANSAC)
+
+
+@pytest.mark.parametrize("solver", [0, 1])
+def test_final_stage_mode(lib, solver):
+    # pnp_epnp_final_body's mode as the host and the batched kernel derived it before they shared opp_pnp_final_mode
+    lib.t_final_mode.restype = ctypes.c_int
+    for n in (0, 3, 4, 5, 6, 7):
+        want = 3 if n < 4 else (0 if n == 4 else (2 if n == 5 else 1))
+        if solver == 0 and n >= 4:
+            want = 0                                        # P3P hypotheses whatever n is (solver 0 never reaches that stage)
+        assert lib.t_final_mode(solver, n) == want, (solver, n)
+
+
+LAYOUT = ("hyp", "valid", "score", "score2", "pts", "hyp_stride", "int_stride", "bytes", "returned")
+
+
+def _pnp_layout(lib, iterations, B, n_total):
+    out = (ctypes.c_ulonglong * 9)()
+    lib.t_pnp_layout.restype = None
+    lib.t_pnp_layout(iterations, B, n_total, out)
+    L = dict(zip(LAYOUT, (int(x) for x in out)))
+    assert L["bytes"] == L["returned"]
+    return L
+
+
+def _align(x):
+    return (x + 255) // 256 * 256
+
+
+@pytest.mark.parametrize("iterations", [1, 63, 64, 2000, 10000])
+@pytest.mark.parametrize("n", [0, 1, 4, 5, 6, 300])
+def test_workspace_layout(lib, iterations, n):
+    L = _pnp_layout(lib, iterations, 1, n)
+    I, nn = max(iterations, 1), max(n, 1)
+    # opp_pnp_ex_workspace_bytes and opp_pnp_workspace_bytes as they were written out before the layout
+    assert L["bytes"] == _align(I * 96) + 3 * _align(I * 4) + _align(nn * 104) + 1024
+    assert L["score2"] + 1024 == _align(I * 96) + 2 * _align(I * 4) + 1024
+    assert _pnp_layout(lib, 0, 0, 0) == _pnp_layout(lib, 1, 1, 1)
+    for B in (1, 3):
+        L = _pnp_layout(lib, iterations, B, n)
+        spans = []
+        for name, stride, per_trial in (("hyp", "hyp_stride", 96), ("valid", "int_stride", 4), ("score", "int_stride", 4),
+                                        ("score2", "int_stride", 4)):
+            assert L[name] % 256 == 0 and L[stride] % 256 == 0 and L[stride] >= per_trial * iterations
+            spans += [(L[name] + b * L[stride], L[name] + b * L[stride] + per_trial * iterations) for b in range(B)]
+        assert L["pts"] % 256 == 0
+        spans.append((L["pts"], L["pts"] + 104 * n))
+        spans.sort()
+        assert spans[0][0] == 0 and all(a[1] <= b[0] for a, b in zip(spans, spans[1:])) and spans[-1][1] <= L["bytes"]
+        assert L["bytes"] == B * (_align(I * 96) + 3 * _align(I * 4)) + _align(nn * 104) + 1024       # opp_pnp_batch_workspace_bytes
+
+
+def test_library_workspace_sizes_are_the_closed_forms():
+    """the exported size functions themselves (they run on the host), at the sizes above and at the clamps"""
+    from onepose_plus_plus_amd import _lib
+    lib = _lib.load()
+    for I in (0, 1, 63, 64, 2000, 10000):
+        assert lib.opp_pnp_workspace_bytes(I) == _align(I * 96) + 2 * _align(I * 4) + 1024           # this one never clamped
+        for n in (0, 1, 4, 5, 6, 300):
+            Ic, nc = max(I, 1), max(n, 1)
+            slabs = _align(Ic * 96) + 3 * _align(Ic * 4)
+            assert lib.opp_pnp_ex_workspace_bytes(I, n) == slabs + _align(nc * 104) + 1024
+            for B in (0, 1, 3):
+                assert lib.opp_pnp_batch_workspace_bytes(I, B, n) == max(B, 1) * slabs + _align(nc * 104) + 1024
+            assert lib.opp_pnp_loransac_workspace_bytes(I, n) == lib.opp_pnp_loransac_batch_workspace_bytes(I, 1, n)
 
 
 def _header_arg_counts():

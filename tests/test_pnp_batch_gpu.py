@@ -313,3 +313,33 @@ def test_two_calls_return_the_same_bytes(scene):
         b = ransac_PnP_batch(K, uv, X, offsets=off, seed=seeds, solver=solver, **KW)
         assert a["pose"].tobytes() == b["pose"].tobytes() and np.array_equal(a["stop"], b["stop"]) and np.array_equal(a["state"], b["state"])
         assert all(np.array_equal(x, y) for x, y in zip(a["inliers"], b["inliers"]))
+
+
+@pytest.mark.parametrize("solver", ["p3p", "epnp", "loransac"])
+def test_the_three_front_doors_agree_with_the_batch_at_one_sample(solver):
+    """ransac_PnP's tuple, ransac_PnP_ex's dict and sample 0 of the solver's batch call at B = 1, byte for byte in pose, inliers
+    and state: the single calls share one Python helper, the batch path does not.  n = 70 carries 30 % outliers and 0.5 px noise
+    and every solver succeeds on it; below the solver's minimum (4 matches, 3 for "loransac") every door reports the failure."""
+    from onepose_plus_plus_amd.pose import loransac_PnP_batch, ransac_PnP, ransac_PnP_batch, ransac_PnP_ex
+    rng = np.random.default_rng(2024)
+    kw = dict(pnp_reprojection_error=THR, iterations=500, seed=3)
+    for n in (0, 3, 4, 5, 6, 70):
+        K, uv, X = _scene(rng, max(n, 1), 0.3 if n == 70 else 0.0, 0.5 if n == 70 else 0.0)[:3]
+        uv[:, 1] = (uv[:, 1] - K[1, 2]) / K[1, 1] * K[0, 0] + K[1, 2]     # one focal length: "loransac" puts fx on both axes
+        K[1, 1] = K[0, 0]
+        uv, X = uv[:n].astype(np.float32), X[:n].astype(np.float32)
+        pose, homo, inl, ok = ransac_PnP(K, uv, X, solver=solver, **kw)
+        ex = ransac_PnP_ex(K, uv, X, solver=solver, **kw)
+        if solver == "loransac":
+            r = loransac_PnP_batch(K[None], uv, X, offsets=[0, n], **kw)
+        else:
+            r = ransac_PnP_batch(K[None], uv, X, offsets=[0, n], solver=solver, **kw)
+        assert ok is ex["state"] and ok == bool(r["state"][0]), n
+        assert pose.dtype == np.float64 and pose.tobytes() == r["pose"][0].tobytes(), n
+        assert homo.tobytes() == r["pose_homo"][0].tobytes(), n
+        assert inl.dtype == r["inliers"][0].dtype and inl.shape == r["inliers"][0].shape and np.array_equal(inl, r["inliers"][0]), n
+        _same_as_single(r, 0, ex)
+        if n == 70:
+            assert ok and len(inl) >= 40, n        # 49 matches carry noise alone, 0.5 px against a 3.3 px threshold
+        if n < (3 if solver == "loransac" else 4):
+            assert not ok and np.array_equal(pose, np.eye(4)[:3]) and inl.size == 0, n
