@@ -12,17 +12,7 @@ __device__ __forceinline__ void pnp_hypotheses_body(const float* __restrict__ p2
                                                     double* __restrict__ hyp, int* __restrict__ valid, int h) {
   if (h >= prm.iters) return;
   int idx[4];
-  unsigned s = hash32(prm.seed ^ (0x9e3779b9u * (unsigned)(h + 1)));
-  for (int k = 0; k < 4; ++k) {
-    for (int tries = 0; tries < 64; ++tries) {
-      s = hash32(s + 0x632be5abu);
-      const int c = (int)(s % (unsigned)prm.n);
-      bool dup = false;
-      for (int j = 0; j < k; ++j) dup |= idx[j] == c;
-      idx[k] = c;
-      if (!dup) break;
-    }
-  }
+  draw_sample<4>(prm.seed, h, prm.n, idx);   // the sampler pnp_p3p_samples_kernel records
   double y[3][3], x[3][3];
   for (int k = 0; k < 3; ++k) {
     const double u = ((double)p2[2 * idx[k]] - prm.K4[2]) / prm.K4[0];

@@ -113,7 +113,7 @@ def _single(K, pts_2d, pts_3d, device, n_cnt, ws_bytes, call, simple_pinhole=Fal
     """One single-sample C call and its device-to-host copy.  cnt = n_inliers, ok(, stop(, the caller's)) is `n_cnt` ints;
     ws_bytes(lib, n) sizes the workspace; record_bufs(device) -> dict of the caller's extra device tensors;
     call(lib, p2, p3, n, K4, out, mask, cnt, bufs, ws, nbytes, stream) -- pointers but for n, bufs and nbytes -- -> (return code, name).
-    -> (dict(pose [3,4], state, inliers [k] int32(, stop)), cnt on the host as float64, bufs)"""
+    -> (dict(pose [3,4], state, n_inliers (the raw count), inliers [k] int32(, stop)), cnt on the host as float64, bufs)"""
     lib = _lib.load()
     device = _device(pts_2d, device)
     Kn = K.detach().cpu().numpy() if torch.is_tensor(K) else np.asarray(K)
@@ -133,7 +133,7 @@ def _single(K, pts_2d, pts_3d, device, n_cnt, ws_bytes, call, simple_pinhole=Fal
         _lib.check(*call(lib, p2.data_ptr(), p3.data_ptr(), n, K4, out.data_ptr(), mask.data_ptr(), cnt.data_ptr(), bufs, ws.data_ptr(),
                          nbytes, stream))
         host = torch.cat([out, cnt.double()]).cpu().numpy()              # one D2H copy
-        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0)}
+        res = {"pose": host[:12].reshape(3, 4).copy(), "state": bool(host[13] != 0), "n_inliers": int(host[12])}
         if n_cnt > 2:
             res["stop"] = int(host[14])
         res["inliers"] = torch.nonzero(mask[:n]).to(torch.int32).cpu().numpy().reshape(-1) if res["state"] else \
@@ -179,7 +179,7 @@ def _loransac(K, pts_2d, pts_3d, pnp_reprojection_error, iterations, seed, devic
 
 def ransac_PnP_ex(K, pts_2d, pts_3d, scale=1, pnp_reprojection_error=5, iterations=10000, refine_iters=8, seed=0, device=None,
                   solver="p3p", confidence=None, record=False, min_trials=1000, min_inlier_ratio=0.01, simple_pinhole=True):
-    """`opp_pnp_ransac_ex` -> dict(pose [3,4], inliers [k] int, state, stop, and with `record` the per-hypothesis
+    """`opp_pnp_ransac_ex` -> dict(pose [3,4], inliers [k] int, n_inliers (the kernel's own count), state, stop, and with `record` the per-hypothesis
     `samples` [iterations, 5] and `scores` [iterations]).  confidence None: 0.99 for "epnp", off for "p3p", 0.9999 for "loransac".
     solver "loransac" (`opp_pnp_loransac`; `scale` and `refine_iters` unused, `min_trials` / `min_inlier_ratio` / `simple_pinhole`
     for it alone: simple_pinhole False uses fx and fy instead of fx for both axes): `stop` = trials the sequential loop runs, and

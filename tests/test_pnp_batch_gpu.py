@@ -48,7 +48,7 @@ def scene():
     Ks, uvs, Xs, gts = _make_batch()
     singles = {}
     for solver in SOLVERS:
-        for conf in (1.0, None):
+        for conf in (1.0, None, 0.99):
             singles[solver, conf] = [ransac_PnP_ex(Ks[b], uvs[b], Xs[b], seed=SEEDS[b], solver=solver, confidence=conf, **KW)
                                      for b in range(len(SIZES))]
     return {"K": Ks, "uv": uvs, "X": Xs, "gt": gts, "singles": singles}
@@ -74,7 +74,7 @@ def _same_as_single(r, i, ref):
     assert np.array_equal(r["pose_homo"][i], np.concatenate([r["pose"][i], [[0.0, 0.0, 0.0, 1.0]]]))
 
 
-@pytest.mark.parametrize("conf", [1.0, None])
+@pytest.mark.parametrize("conf", [1.0, None, 0.99])
 @pytest.mark.parametrize("solver", SOLVERS)
 def test_every_sample_equals_the_single_call(scene, solver, conf):
     from onepose_plus_plus_amd.pose import ransac_PnP, ransac_PnP_batch
@@ -89,6 +89,8 @@ def test_every_sample_equals_the_single_call(scene, solver, conf):
     for b, n in enumerate(SIZES):
         assert n >= 4 or not r["state"][b]                        # fewer than 4 matches: the failure convention
         assert n < 100 or r["state"][b]
+    if solver == "p3p" and conf == 0.99:                          # pnp_batch_stop_kernel with an early stop on the P3P path
+        assert any(int(r["stop"][b]) < ITERS for b in range(B) if SIZES[b] >= 4)
     if solver == "p3p" and conf is None:                          # the default path against ransac_PnP's tuple
         for b in range(B):
             pose, homo, inl, ok = ransac_PnP(scene["K"][b], scene["uv"][b], scene["X"][b], seed=SEEDS[b], **KW)
