@@ -346,6 +346,23 @@ int opp_linear_attention_train_backward(const float* q, const float* k, const fl
                                         float* grad_q, float* grad_k, float* grad_v, void* workspace, size_t workspace_bytes,
                                         void* stream);
 
+/* ---- training step: FullAttention.forward with its backward (loftr_module/linear_attention.py:64-95; no mask, no dropout) --
+ * Raw projections q [B][L][nhead][D], k, v [B][S][nhead][D] (fp32, contiguous, 16-byte aligned): per head
+ * out = softmax(q k^T / sqrt(D)) v.  forward also returns lse [B][nhead][L] = log2 sum_s 2^(logit_s log2 e) (BASE 2; x ln 2 = the
+ * natural log-sum-exp of the scaled logits), which backward takes back together with out and grad_out [B][L][nhead][D]; it
+ * rebuilds the probabilities tile by tile (nothing of size L x S is allocated; the workspace holds delta [B][nhead][L] =
+ * sum_d grad_out out) and writes grad_q, grad_k, grad_v without atomics (bit-identical from call to call).
+ * precision as opp_full_attention: 0 = fp32 MFMA, 3 = bf16x3; anything else OPP_ERR_UNSUPPORTED.  D = 32 with a stream longer
+ * than 32 rows runs on MFMA kernels (csrc/full_attention_train.hip); shorter streams and D = 16 with both streams <= 64 rows on
+ * exact-fp32 vector kernels in both precisions.  Every other shape (D = 16 with a longer stream, another D, B > 65535) returns
+ * OPP_ERR_UNSUPPORTED before any launch, and the workspace size of such a shape is 0. */
+size_t opp_full_attention_train_workspace_bytes(int B, int L, int S, int nhead, int D);
+int opp_full_attention_train_forward(const float* q, const float* k, const float* v, int B, int L, int S, int nhead, int D, int precision,
+                                     float* out, float* lse, void* workspace, size_t workspace_bytes, void* stream);
+int opp_full_attention_train_backward(const float* q, const float* k, const float* v, const float* out, const float* lse,
+                                      const float* grad_out, int B, int L, int S, int nhead, int D, int precision, float* grad_q,
+                                      float* grad_k, float* grad_v, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- training step: ResNet-FPN forward that keeps its activations, and its backward ---------------------------------------
  * PL_OnePosePlus.training_step (src/lightning_model/OnePosePlus_lightning_model.py:54-81) differentiates the loss through
  * ResNetFPN_8_2.forward (backbone/resnet.py:141-164): nn.Conv2d (no bias), nn.BatchNorm2d in train(), ReLU / LeakyReLU(0.01),

@@ -2449,6 +2449,32 @@ extern "C" int opp_linear_attention_train_backward(const float* q, const float* 
                                (hipStream_t)stream);
 }
 
+extern "C" size_t opp_full_attention_train_workspace_bytes(int B, int L, int S, int nhead, int D) { return opp_fullattn_train_ws_bytes(B, L, S, nhead, D); }
+
+// precision as opp_full_attention: 0 (fp32) or 3 (bf16x3); -1 = refused
+static int full_attention_train_prec(const char* what, int precision) {
+  if (precision == 0) return OPP_PREC_FP32;
+  if (precision == 3) return OPP_PREC_BF16X3;
+  opp_set_error("%s: precision must be 0 (fp32) or 3 (bf16x3), got %d", what, precision);
+  return -1;
+}
+
+extern "C" int opp_full_attention_train_forward(const float* q, const float* k, const float* v, int B, int L, int S, int nhead, int D, int precision,
+                                                float* out, float* lse, void* ws, size_t ws_bytes, void* stream) {
+  (void)ws, (void)ws_bytes;
+  const int prec = full_attention_train_prec("full_attention_train_forward", precision);
+  if (prec < 0) return OPP_ERR_UNSUPPORTED;
+  return opp_fullattn_train_fwd(q, k, v, B, L, S, nhead, D, prec, out, lse, (hipStream_t)stream);
+}
+
+extern "C" int opp_full_attention_train_backward(const float* q, const float* k, const float* v, const float* out, const float* lse,
+                                                 const float* grad_out, int B, int L, int S, int nhead, int D, int precision, float* grad_q,
+                                                 float* grad_k, float* grad_v, void* ws, size_t ws_bytes, void* stream) {
+  const int prec = full_attention_train_prec("full_attention_train_backward", precision);
+  if (prec < 0) return OPP_ERR_UNSUPPORTED;
+  return opp_fullattn_train_bwd(q, k, v, out, lse, grad_out, B, L, S, nhead, D, prec, grad_q, grad_k, grad_v, ws, ws_bytes, (hipStream_t)stream);
+}
+
 extern "C" int opp_conv_packed_k(int cin, int ks) { return opp_conv_k(cin, ks); }
 
 extern "C" int opp_pack_h2(const float* in, float* out, size_t n, float* scale2, void* stream) {

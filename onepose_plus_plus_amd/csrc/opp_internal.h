@@ -74,6 +74,13 @@ bool opp_linattn_small_ok(int len0, int len1, int C, int D);
 // qkv [n_seg * (len0 + len1)][3 C] = plain Q | K | V, msg [same rows][C]; prec OPP_PREC_FP32 or OPP_PREC_BF16X3; D = C / nhead in {16, 32}
 int opp_full_attention_run(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross, int prec, float* msg,
                            hipStream_t stream);
+// full_attention_train.hip -- FullAttention of the training step on raw q [B][L][H][D], k, v [B][S][H][D]: forward that also returns
+// lse [B][H][L] (base 2), and the backward that rebuilds the probabilities from it (delta [B][H][L] in the workspace)
+size_t opp_fullattn_train_ws_bytes(int B, int L, int S, int H, int D);
+int opp_fullattn_train_fwd(const float* q, const float* k, const float* v, int B, int L, int S, int H, int D, int prec, float* out, float* lse,
+                           hipStream_t stream);
+int opp_fullattn_train_bwd(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* go, int B, int L,
+                           int S, int H, int D, int prec, float* gq, float* gk, float* gv, void* ws, size_t ws_bytes, hipStream_t stream);
 int opp_linattn_small_pair(const float* qkv, int ld, int n_seg, int len0, int len1, int cross, float* out, int ldo, int C, int D,
                            float eps, hipStream_t stream);
 int opp_linattn_apply_pair(const float* qkv, int ld, const float* kv, const float* ks, int cross, float* out, int ldo,

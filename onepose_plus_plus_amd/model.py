@@ -391,8 +391,9 @@ class OnePosePlus_model(nn.Module):
                 raise TypeError("full attention with query_image_mask: upstream FullAttention indexes the None q_mask of the cross "
                                 "layers ('NoneType' object is not subscriptable, linear_attention.py:84-85)")
             raise NotImplementedError("full attention with query_image_mask and self-only layers (NaN rows upstream) is not supported")
-        if self.training:
-            # the autograd graph (train_autograd.py) has linear-attention backward kernels only
+        if self.training and not getattr(self, "full_attention_training", False):
+            # opt-in (`full_attention_training = True`): the autograd graph then builds HipFullAttention nodes (train_autograd.py,
+            # csrc/full_attention_train.hip) at the full levels, and the no-grad train forward runs opp_transformer as in eval
             raise NotImplementedError("full attention: training is not implemented")
 
     def _ensure_ready(self, device, scope=0):
@@ -604,6 +605,9 @@ class OnePosePlus_model(nn.Module):
     # the matches' device; tests inject recorded draws so that both implementations select the same indices)
     train_randint = staticmethod(torch.randint)
     bn_momentum = 0.1            # torch.nn.BatchNorm2d default, used by every BatchNorm of resnet.py
+    # opt-in: a train()-mode forward of a configuration with `attention` other than "linear" at a level.  False (default): refused
+    # (`_check_full_attention`); True: the training graph builds `train_autograd.HipFullAttention` nodes at those levels
+    full_attention_training = False
 
     def _update_running_stats(self, lib, ctx, stats):
         """running statistics after a train()-mode forward, like torch.nn.BatchNorm2d: stats [n_bn, 512] = batch mean | unbiased variance"""

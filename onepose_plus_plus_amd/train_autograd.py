@@ -10,6 +10,8 @@ the step runs in a PyTorch (MIOpen / rocBLAS) operator:
                         input / weight gradients, BatchNorm + activation backward, upsample transpose (csrc/conv_bwd.hip)
   `HipLinear`           every Linear of the two transformers and of the keypoint encoder (csrc/linear_bwd.hip)
   `HipLinearAttention`  csrc/linattn_train.hip
+  `HipFullAttention`    `attention` other than "linear" at a level (opt-in: `OnePosePlus_model.full_attention_training`): flash-style forward
+                        that keeps the softmax log-sum-exp, backward that rebuilds the probabilities from it (csrc/full_attention_train.hip)
   `HipLayerNorm`        csrc/train_misc.hip
   `HipCoarseMatch`      score GEMM + dual softmax + mutual-nearest-neighbour selection = the inference kernels (opp_coarse_match);
                         backward = dual-softmax backward (csrc/loss.hip) + the two feature gradients on the Linear-backward GEMMs
@@ -17,7 +19,7 @@ the step runs in a PyTorch (MIOpen / rocBLAS) operator:
   `HipFineHead`         FineMatching's expectation head (heatmap softmax, spatial expectation, std) forward + backward (csrc/fine.hip, r05)
 PyTorch supplies the tape (autograd), elementwise glue (residual adds, ReLU) and index plumbing.
 
-The helpers `_linear` / `_layer_norm` / `_kpt_encoding` / `_linear_attention` / `_encoder_layer` / `_transformer` / `DualSoftmax` fall
+The helpers `_linear` / `_layer_norm` / `_kpt_encoding` / `_linear_attention` / `_full_attention` / `_encoder_layer` / `_transformer` / `DualSoftmax` fall
 back to plain torch ops for CPU tensors (hp = None): that is how tests/torch_graph_ref.py -- the functional restatement of the whole
 graph the tests differentiate against the reference's own gradients -- reuses them; the restatement itself (plain-torch backbone,
 `differentiable_forward`) is test infrastructure and lives under tests/.
@@ -132,6 +134,59 @@ class HipLinearAttention(torch.autograd.Function):
         return gq, gk, gv, None, None
 
 
+_FULL_ATTN_PRECISION = {2: 3, 0: 0}      # hp -> `precision` of opp_full_attention / opp_full_attention_train_* (3 = bf16x3, 0 = fp32)
+
+
+def _full_attention_supported(B, L, S, H, D):
+    """the shapes opp_full_attention_train_* take (include/opp_hip.h): the ABI reports a workspace size of 0 for every other one"""
+    from . import _lib
+    return _lib.load().opp_full_attention_train_workspace_bytes(B, L, S, H, D) > 0
+
+
+class HipFullAttention(torch.autograd.Function):
+    """FullAttention.forward (loftr_module/linear_attention.py:64-95; no mask, no dropout) with forward and backward in libopp_hip.so
+    (csrc/full_attention_train.hip): q [B, L, H, D], k, v [B, S, H, D] raw projections.  Kept for the backward: q, k, v, out and the
+    log-sum-exp of every softmax row [B, H, L] -- the probabilities are rebuilt tile by tile, no L x S tensor exists."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, hp):
+        from . import _lib
+        lib = _lib.load()
+        dev = q.device
+        qc, kc, vc = (t.to(torch.float32).contiguous() for t in (q, k, v))
+        B, L, H, D = qc.shape
+        S = kc.shape[1]
+        out = torch.empty_like(qc)
+        lse = torch.empty((B, H, L), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.opp_full_attention_train_forward(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), B, L, S, H, D, _FULL_ATTN_PRECISION[hp],
+                                                            out.data_ptr(), lse.data_ptr(), None, 0,
+                                                            torch.cuda.current_stream(dev).cuda_stream), "opp_full_attention_train_forward")
+        ctx.save_for_backward(qc, kc, vc, out, lse)
+        ctx.hp = hp
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        from . import _lib
+        lib = _lib.load()
+        qc, kc, vc, out, lse = ctx.saved_tensors
+        dev = qc.device
+        B, L, H, D = qc.shape
+        S = kc.shape[1]
+        gc = g.to(torch.float32).contiguous()
+        gq, gk, gv = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+        nb = lib.opp_full_attention_train_workspace_bytes(B, L, S, H, D)
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.opp_full_attention_train_backward(qc.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                                             gc.data_ptr(), B, L, S, H, D, _FULL_ATTN_PRECISION[ctx.hp], gq.data_ptr(),
+                                                             gk.data_ptr(), gv.data_ptr(), ws.data_ptr(), nb,
+                                                             torch.cuda.current_stream(dev).cuda_stream), "opp_full_attention_train_backward")
+        need = ctx.needs_input_grad
+        return gq if need[0] else None, gk if need[1] else None, gv if need[2] else None, None
+
+
 class HipLayerNorm(torch.autograd.Function):
     """nn.LayerNorm(C) (loftr_module/transformer.py:87-88, :92-94; eps 1e-5) over the last axis, C in (64, 128, 256), forward and
     backward in libopp_hip.so (csrc/train_misc.hip: one wave per row; d gamma / d beta as a fixed-order reduction over the rows)."""
@@ -231,6 +286,14 @@ def _linear_attention(q, k, v, q_mask=None, kv_mask=None, eps=1e-6, hp=None):   
     return torch.einsum("nlhd,nhdv,nlh->nlhv", Q, KV, Z) * S
 
 
+def _full_attention(q, k, v, hp=None):      # loftr_module/linear_attention.py:64-95 with q_mask = kv_mask = None, use_dropout = False
+    if hp is not None and q.is_cuda and _full_attention_supported(q.shape[0], q.shape[1], k.shape[1], q.shape[2], q.shape[3]):
+        return HipFullAttention.apply(q, k, v, hp)
+    QK = torch.einsum("nlhd,nshd->nlsh", q, k)
+    A = torch.softmax((1.0 / q.size(3) ** 0.5) * QK, dim=2)
+    return torch.einsum("nlsh,nshd->nlhd", A, v).contiguous()
+
+
 def _norm_affine(p, name, ref):
     """(weight, bias) of a layer norm; norm_method "instancenorm" has no such keys (nn.InstanceNorm1d(d_model) on [N, L, C] tokens = the
     same per-token normalisation without affine): constant ones / zeros, which need no gradient"""
@@ -240,7 +303,8 @@ def _norm_affine(p, name, ref):
     return ref.new_ones(C), ref.new_zeros(C)
 
 
-def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=None):      # loftr_module/transformer.py:65-94
+def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=None, attention="linear"):      # loftr_module/transformer.py:65-94
+    """attention: the level's `attention` setting; any value but "linear" builds FullAttention upstream (transformer.py:29-38)"""
     B, _, C = x.shape
     D = C // nhead
     wq, wk, wv = p[name + ".q_proj.weight"], p[name + ".k_proj.weight"], p[name + ".v_proj.weight"]
@@ -257,7 +321,12 @@ def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=
         q = _linear(x, wq).view(B, -1, nhead, D)
         k = _linear(source, wk).view(B, -1, nhead, D)
         v = _linear(source, wv).view(B, -1, nhead, D)
-    msg = _linear_attention(q, k, v, x_mask, source_mask, hp=hp).reshape(B, -1, C)
+    if attention == "linear":
+        msg = _linear_attention(q, k, v, x_mask, source_mask, hp=hp).reshape(B, -1, C)
+    else:
+        if x_mask is not None or source_mask is not None:       # upstream cannot run it either (model.py: _check_full_attention)
+            raise NotImplementedError("full attention takes no mask")
+        msg = _full_attention(q, k, v, hp=hp).reshape(B, -1, C)
     msg = _layer_norm(_linear(msg, p[name + ".merge.weight"], hp), *_norm_affine(p, name + ".norm1", x), hp)
     msg = _linear(F.relu(_linear(torch.cat([x, msg], dim=2), p[name + ".mlp.0.weight"], hp)), p[name + ".mlp.2.weight"], hp)
     msg = _layer_norm(msg, *_norm_affine(p, name + ".norm2", x), hp)
@@ -267,13 +336,15 @@ def _encoder_layer(p, name, nhead, x, source, x_mask=None, source_mask=None, hp=
 
 
 def _transformer(p, name, tcfg, f3, f2, mask=None, hp=None):      # loftr_module/transformer.py:133-171 (f3 already [B, N, C])
+    att = tcfg.get("attention", "linear")
     for i, kind in enumerate(list(tcfg["layer_names"]) * tcfg["layer_iter_n"]):
         n = "%s.layers.%d" % (name, i)
         if kind == "self":
-            f2, f3 = _encoder_layer(p, n, tcfg["nhead"], f2, f2, mask, mask, hp), _encoder_layer(p, n, tcfg["nhead"], f3, f3, hp=hp)
+            f2, f3 = (_encoder_layer(p, n, tcfg["nhead"], f2, f2, mask, mask, hp, attention=att),
+                      _encoder_layer(p, n, tcfg["nhead"], f3, f3, hp=hp, attention=att))
         else:       # cross: both streams from the pre-update tensors (quirk q6)
-            f2, f3 = (_encoder_layer(p, n, tcfg["nhead"], f2, f3, x_mask=mask, hp=hp),
-                      _encoder_layer(p, n, tcfg["nhead"], f3, f2, source_mask=mask, hp=hp))
+            f2, f3 = (_encoder_layer(p, n, tcfg["nhead"], f2, f3, x_mask=mask, hp=hp, attention=att),
+                      _encoder_layer(p, n, tcfg["nhead"], f3, f2, source_mask=mask, hp=hp, attention=att))
     return f3, f2
 
 
