@@ -673,6 +673,48 @@ int opp_pose_metrics(const float* model_pts, int n_points, const double* pose_pr
                      const unsigned char* syn, const unsigned char* valid, int n_poses, double t_to_cm, double* out,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- parameter update of the training step ---------------------------------
+ * PyTorch's Adam / AdamW (optimizers/optimizers.py:4-13) behind its clip_grad_norm_ (Lightning's
+ * `gradient_clip_val: 0.5`, train.yaml:32) over a LIST of fp32 tensors: one launch for the global gradient norm, one for
+ * the update.  Both walk two DEVICE tables: one opp_optim_tensor per tensor and one opp_optim_chunk per workgroup; a chunk
+ * is at most OPP_OPTIM_CHUNK elements of one tensor.  No atomics: the same inputs give the same bits. */
+#define OPP_OPTIM_CHUNK 8192
+typedef struct opp_optim_tensor {
+  float* p;                /* parameter, n floats */
+  const float* g;          /* its gradient (read only) */
+  float* m;                /* first moment (exp_avg) */
+  float* v;                /* second moment (exp_avg_sq) */
+  long long n;
+} opp_optim_tensor;
+typedef struct opp_optim_chunk {
+  int tensor;              /* index into the tensor table */
+  int len;                 /* 1..OPP_OPTIM_CHUNK elements */
+  long long start;         /* first element, a multiple of OPP_OPTIM_CHUNK */
+} opp_optim_chunk;
+/* The chunk length the library was built with (OPP_OPTIM_CHUNK). */
+int opp_optim_chunk_elems(void);
+/* The chunk table of a list of tensors -- a pure host function of the element counts numel [n_tensors], callable without a
+ * device: tensor t gets ceil(numel[t] / OPP_OPTIM_CHUNK) consecutive chunks in tensor order (an empty tensor none), no chunk
+ * spans two tensors.  *n_chunks receives their number; chunks (HOST array of max_chunks entries) may be NULL for the count
+ * alone.  The caller copies the table to the device. */
+int opp_optim_plan(const long long* numel, int n_tensors, opp_optim_chunk* chunks, long long max_chunks, long long* n_chunks);
+/* partials[c] = grad_scale^2 x (sum of the squares of chunk c's gradient elements), accumulated in double: one slot per
+ * workgroup, n_chunks doubles on the device.  Replaces the foreach norm + stack + norm of clip_grad_norm_. */
+int opp_grad_sqnorm(const opp_optim_tensor* tensors, const opp_optim_chunk* chunks, int n_chunks, double grad_scale,
+                    double* partials, void* stream);
+/* One Adam (decoupled = 0: g' += wd p) or AdamW (decoupled != 0: p *= 1 - lr wd) step of the chunks [0, n_chunks) of
+ * `chunks`, per element in fp32 in the order of operations of PyTorch's single-tensor Adam:
+ *   g' = g grad_scale coef;  m += (g' - m)(1 - beta1);  v = v beta2 + (1 - beta2) g' g';
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps),      bc1 = 1 - beta1^t, bc2 = 1 - beta2^t from the caller (host doubles).
+ * g is not written.  n_partials > 0 clips: every workgroup sums partials [0, n_partials) (opp_grad_sqnorm over ALL tensors
+ * of the step, whichever subset `chunks` covers) in index order, total_norm = sqrt(sum), coef = min(1, max_norm /
+ * (total_norm + 1e-6)) as clip_grad_norm_ forms it, and workgroup 0 stores total_norm to norm_out (1 float, may be NULL);
+ * a NaN norm propagates.  n_partials = 0: coef = 1, nothing is stored.  `chunks` may point into the middle of a table
+ * (one launch per parameter group); chunk.tensor always indexes `tensors`. */
+int opp_adam_step(const opp_optim_tensor* tensors, const opp_optim_chunk* chunks, int n_chunks, const double* partials,
+                  int n_partials, double max_norm, float* norm_out, double grad_scale, double lr, double beta1, double beta2,
+                  double eps, double weight_decay, int decoupled, double bc1, double bc2, void* stream);
+
 /* Tuning aid (libraries built with -DOPP_TUNING only; otherwise returns an error): device buffer (4 x uint64 per
  * wave) for the phase time stamps written by the timed conv variants (tile_cfg 120 = 256x128 / 8 waves,
  * 121 = 128x128 / 4 waves, 122 = 128x128 / 8 waves); NULL disables. */

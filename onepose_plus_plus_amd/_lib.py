@@ -54,6 +54,16 @@ class OppLoRecord(Structure):
                                         "cand_taken", "ransac_pose", "lm_iters")]
 
 
+class OppOptimTensor(Structure):
+    """one row of the optimizer's tensor table (include/opp_hip.h `opp_optim_tensor`)"""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_longlong)]
+
+
+class OppOptimChunk(Structure):
+    """one row of the optimizer's chunk table (include/opp_hip.h `opp_optim_chunk`)"""
+    _fields_ = [("tensor", c_int), ("len", c_int), ("start", c_longlong)]
+
+
 # name -> (restype, argtypes).  Must list every symbol declared in include/opp_hip.h
 # (tests/test_cabi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -202,6 +212,11 @@ SIGNATURES = {
     "opp_fine_window_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "opp_fine_window_gather_backward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                                 c_void_p, c_void_p]),
+    "opp_optim_chunk_elems": (c_int, []),
+    "opp_optim_plan": (c_int, [c_void_p, c_int, c_void_p, c_longlong, POINTER(c_longlong)]),
+    "opp_grad_sqnorm": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "opp_adam_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, ctypes.c_double, c_void_p] + [ctypes.c_double] * 6
+                      + [c_int, ctypes.c_double, ctypes.c_double, c_void_p]),
     "opp_profile_start": (c_int, [c_int, c_int, c_int]),
     "opp_profile_stop": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int)]),
 }

@@ -17,7 +17,8 @@ refinement, the reference's pycolmap branch; `pnp="auto"`: whichever of the two 
 the reference would; `pnp=True`: the default P3P solver); with `metrics=True` (off by default) `compute_query_pose_errors` itself is replaced
 by a wrapper around `onepose_plus_plus_amd.metrics.compute_query_pose_errors`, which scores the poses on the device; with
 `loss=True` the training step's `Loss` (src/lightning_model/losses.py) and `fine_supervision`
-(src/models/OnePosePlus/utils/fine_supervision.py) resolve to `onepose_plus_plus_amd.losses`.
+(src/models/OnePosePlus/utils/fine_supervision.py) resolve to `onepose_plus_plus_amd.losses`; with `optimizer=True` (off by default)
+`build_optimizer` / `build_scheduler` (src/models/OnePosePlus/optimizers/optimizers.py) resolve to `onepose_plus_plus_amd.optim`.
 
 If the reference modules were imported already their attributes are patched in place; otherwise light-weight module
 objects are registered under those names, so the reference's own model files (and their kornia / timm imports) are
@@ -105,13 +106,16 @@ def _metrics_wrapper(pnp):
     return compute_query_pose_errors
 
 
-def install(pnp=True, loss=True, metrics=False):
+def install(pnp=True, loss=True, metrics=False, optimizer=False):
     """-> dict of what was patched (for logging / tests).  pnp: True (P3P solver), "epnp" (the reference's EPnP), "loransac" (its
     pycolmap branch), "auto" (the one of the two that the caller's `use_pycolmap_ransac` selects) or False.  metrics: True also
     replaces `src.utils.metric_utils.compute_query_pose_errors` by the on-device scoring of `onepose_plus_plus_amd.metrics`
     (recorded under "src.utils.metric_utils:compute_query_pose_errors") and rebinds the name in the reference's two callers when
     they were imported already (recorded under "<module>:compute_query_pose_errors"); off by default.  With `pnp=False` the
-    wrapper scores the poses of the reference's own `ransac_PnP` (OpenCV / pycolmap) on the device"""
+    wrapper scores the poses of the reference's own `ransac_PnP` (OpenCV / pycolmap) on the device.  optimizer: True makes
+    `src.models.OnePosePlus.optimizers.optimizers` a stand-in that holds `onepose_plus_plus_amd.optim.build_optimizer` /
+    `build_scheduler` (`configure_optimizers`, OnePosePlus_lightning_model.py:162-165, then returns a `FusedAdam`) and rebinds
+    the two names in the Lightning module when it was imported already; off by default"""
     done = {}
     for path in _MODEL_PATHS:
         mod = sys.modules.get(path)
@@ -168,4 +172,23 @@ def install(pnp=True, loss=True, metrics=False):
         if lm is not None:          # imported before install(): its module-level names were bound already
             lm.Loss, lm.fine_supervision = Loss, fine_supervision
             done["src.lightning_model.OnePosePlus_lightning_model"] = "Loss, fine_supervision"
+    if optimizer:
+        from .optim import build_optimizer, build_scheduler
+        path = "src.models.OnePosePlus.optimizers.optimizers"
+        standin = types.ModuleType(path)                 # replaces the reference's file even when it was imported already
+        standin.build_optimizer, standin.build_scheduler = build_optimizer, build_scheduler
+        parent = "src.models.OnePosePlus.optimizers"
+        pkg = sys.modules.get(parent)
+        if pkg is None:
+            pkg = types.ModuleType(parent)
+            pkg.__path__ = _real_dirs(parent)
+            sys.modules[parent] = pkg
+            setattr(sys.modules["src.models.OnePosePlus"], "optimizers", pkg)
+        sys.modules[path] = standin
+        pkg.optimizers = standin
+        done[path] = "build_optimizer, build_scheduler"
+        lm = sys.modules.get("src.lightning_model.OnePosePlus_lightning_model")
+        if lm is not None:          # imported before install(): OnePosePlus_lightning_model.py:10-13 bound the names already
+            lm.build_optimizer, lm.build_scheduler = build_optimizer, build_scheduler
+            done["src.lightning_model.OnePosePlus_lightning_model:build_optimizer"] = "build_optimizer, build_scheduler"
     return done

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--optimizer", default="torch", choices=["torch", "fused"],
+                    help="torch: torch.optim.AdamW (the committed numbers); fused: onepose_plus_plus_amd.optim.FusedAdam, same hyper-parameters")
     args = ap.parse_args()
     from onepose_plus_plus_amd import OnePosePlus_model, default_config
     from onepose_plus_plus_amd.losses import Loss, fine_supervision
@@ -60,7 +62,11 @@ def main():
                                             "focal_alpha": 0.5, "focal_gamma": 2.0, "pos_weight": 1.0, "neg_weight": 1.0, "fine_correct_thr": 1.0}}
     loss_mod = Loss(hparams["loss"]).train()
     avg = GradientAverager(model)                                            # broadcast of rank 0's parameters / buffers + the flat gradient buffer
-    opt = torch.optim.AdamW(model.parameters(), lr=1e-6)
+    if args.optimizer == "fused":
+        from onepose_plus_plus_amd.optim import FusedAdam
+        opt = FusedAdam(model.parameters(), lr=1e-6, weight_decay=1e-2, decoupled=True, module=model)
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=1e-6)
     t_reduce = [0.0]
 
     def step():
@@ -98,7 +104,7 @@ def main():
     if rank == 0:
         step_ms = float(el.item()) / args.steps * 1e3
         print(json.dumps({"metric": "training samples/s, data-parallel (BASELINE configs[4] shape)", "value": round(world * B / step_ms * 1e3, 2),
-                          "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 2),
+                          "unit": "samples/s", "n_gpus": world, "optimizer": args.optimizer, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(step_ms, 2),
                           "scaling": "weak", "per_gpu_batch": B, "n_points": N, "allreduce_ms_per_step": round(t_reduce[0] / args.steps * 1e3, 3),
                           "parameters_identical_across_ranks": bool(float(lo.item()) == float(hi.item())), "loss": round(loss, 5)}), flush=True)
     dist.destroy_process_group()
