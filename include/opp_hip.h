@@ -448,6 +448,32 @@ int opp_build_assignmatrix(const float* kp2d_coarse, const float* kp2d_fine, int
                            int w_c, float scale_x, float scale_y, float coarse_scale, short* conf_gt, float* fine_loc_gt,
                            long long* keys, int* status, void* stream);
 
+/* ---- a training sample's tensors from its annotation arrays (the training branch of OnePosePlusDataset.read_anno,
+ * src/datasets/OnePosePlus_dataset.py:341-437, in front of opp_build_assignmatrix; csrc/train_sample.hip) ----------------
+ * kornia 0.4.1's homography_warp of B fp32 images [B][1][h][w] in one launch (restated: kornia is not pinned in this project).  src: rows
+ * src_stride floats apart, images src_batch_stride floats apart; src_homo_dst [B][3][3] row-major fp32 ON THE DEVICE, the NORMALISED matrix
+ * the reference passes (the inverse of normalize_homography(H)); dst [B][h][w] dense.  Destination grid linspace(-1, 1, w) x
+ * linspace(-1, 1, h); transform_points with scale 1 / z where |z| > 1e-8, else 1; grid_sample(bilinear, zeros, align_corners).  The identity
+ * with align_corners != 0 returns the input bit for bit.  h, w >= 2. */
+int opp_homography_warp(const float* src, int B, int h, int w, int src_stride, long long src_batch_stride, const float* src_homo_dst,
+                        int align_corners, float* dst, void* stream);
+/* mkpts_proj [k][2] fp32: pair t's 3D point keypoints3d[assign[1][t]] ([n3d][3] fp32, assign [2][k] int64, both on the device) through
+ * K (R X + t) with x / (z + 1e-6), then -- homography_px != NULL -- through that pixel-space homography with the division by its third row.
+ * pose_Rt [3][4], K [3][3], homography_px [3][3]: row-major fp32 in HOST memory, read before the call returns.  Arithmetic in double from the
+ * fp32 inputs.  A 3D index out of range gives NaN and ORs bit 0 into *status (device int, may be NULL; not zeroed here). */
+int opp_project_pairs(const float* keypoints3d, int n3d, const long long* assign, int k, const float* pose_Rt, const float* K,
+                      const float* homography_px, float* mkpts_proj, int* status, void* stream);
+/* The pairs that survive read_anno's filters, exactly (:393-433): warped != 0 drops unrounded points < 0, > w - 1, > h - 1; then
+ * r = round_half_even(p / cell) * cell in fp32 and the same bounds on r; of the pairs with one r (-0.0 = 0.0) the smallest index stays; the
+ * survivors are ordered by (r.x, r.y) as np.unique(axis=0) orders them.  assign_out [2][k] int64 (row stride k): the k' survivors'
+ * columns, then k - k' columns (0, INT64_MAX) that opp_build_assignmatrix drops silently -- so it takes assign_out with the same k and no
+ * host round trip; *n_out = k' (device int).  kp2d_coarse / kp2d_fine [n2d][2] fp32: rows assign_out[0][:k'] receive r / p, the last
+ * survivor in that order where a 2D index repeats; other rows are untouched (upstream: the input coarse keypoints / zeros).  scratch:
+ * (h / cell + 1) (w / cell + 1) + n2d ints.  *status (device int, may be NULL, not zeroed here): bit 0 = a non-finite point or a 2D index
+ * out of range (upstream raises).  h, w multiples of cell.  One workgroup; deterministic. */
+int opp_select_pairs(const float* mkpts_proj, const long long* assign, int k, int h, int w, int cell, int warped, int n2d,
+                     float* kp2d_coarse, float* kp2d_fine, long long* assign_out, int* n_out, int* scratch, int* status, void* stream);
+
 /* ---- building blocks (exported for stage-level parity tests and tuning) ------------------ */
 /* NHWC convolution as implicit GEMM on the MFMA.  x [Hin][Win][cin_pad], cin_pad = cin rounded up to 32 (pad
  * channels zero); w_packed [cout_pad][opp_conv_packed_k(cin, ks)] (from opp_pack_conv_weight with the same cin:

@@ -118,6 +118,11 @@ SIGNATURES = {
     "opp_fine_head_train_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "opp_build_assignmatrix": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "opp_homography_warp": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_longlong, c_void_p, c_int, c_void_p, c_void_p]),
+    "opp_project_pairs": (c_int, [c_void_p, c_int, c_void_p, c_int, POINTER(c_float), POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
+                                  c_void_p]),
+    "opp_select_pairs": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
     "opp_set_fine_patch_buffers": (c_int, [c_void_p, c_void_p, c_void_p]),
     "opp_fine_patch_buffer_floats": (c_size_t, [c_void_p, c_int, c_int, c_int]),
     "opp_fine_patches_workspace_bytes": (c_size_t, [c_void_p, c_int]),
