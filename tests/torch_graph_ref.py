@@ -72,12 +72,19 @@ def differentiable_forward(p, cfg, inputs, matches, pe, bn_eval_stats=None):
     b_ids, i_ids, j_ids = matches
     if b_ids.numel() == 0:
         return conf, None
+    stride = feat_f.shape[2] // feat_c.shape[2]
+    return conf, fine_level_ref(p, cfg, feat_f, inputs["descriptors3d_db"], b_ids, i_ids, j_ids, stride)
+
+
+def fine_level_ref(p, cfg, feat_f, bank_f, b_ids, i_ids, j_ids, stride, with_var=False):
+    """The fine half of `differentiable_forward`: FinePreprocess -> loftr_fine -> FineMatching._s2d_heatmap on the fine map feat_f
+    [B, Cf, Hf, Wf] (NCHW), the RAW fine bank bank_f [B, Cf, N] and the match list -> expec_f [M', 3].  `stride` = fine pixels per coarse
+    cell.  with_var: also the heatmap variances [M', 2] the std column takes the root of (before the clamp)."""
     fcfg = cfg["loftr_fine"]
     W, Cf = fcfg["window_size"], fcfg["d_model"]
-    stride = feat_f.shape[2] // feat_c.shape[2]
     win = F.unfold(feat_f, kernel_size=(W, W), stride=stride, padding=W // 2)       # fine_preprocess.py:41-55
     win = win.view(feat_f.shape[0], Cf, W * W, -1).permute(0, 3, 2, 1)[b_ids, j_ids]
-    g3 = inputs["descriptors3d_db"].permute(0, 2, 1)[b_ids, i_ids].unsqueeze(1)      # [M', 1, C]: the RAW fine bank (quirk q8)
+    g3 = bank_f.permute(0, 2, 1)[b_ids, i_ids].unsqueeze(1)                          # [M', 1, C]: the RAW fine bank (quirk q8)
     if fcfg["enable"]:
         g3, win = _transformer(p, "loftr_fine", fcfg, g3, win)
     f0 = g3[:, g3.shape[1] // 2, :]                                                  # fine_matching.py:63-68
@@ -88,4 +95,5 @@ def differentiable_forward(p, cfg, inputs, matches, pe, bn_eval_stats=None):
     grid = torch.stack([gx, gy], dim=-1)
     var = torch.sum(grid[None] ** 2 * heat[:, :, None], dim=1) - coords ** 2
     std = torch.sum(torch.sqrt(torch.clamp(var, min=1e-10)), -1)                      # fine_matching.py:92-94
-    return conf, torch.cat([coords, std[:, None]], -1)
+    expec = torch.cat([coords, std[:, None]], -1)
+    return (expec, var.detach()) if with_var else expec
