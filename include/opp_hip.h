@@ -579,6 +579,36 @@ int opp_crop_warp_u8(const unsigned char* src, int h, int w, int src_stride, con
  * axis-0 mean, i.e. bit-identical to the reference.  offsets: n_seg + 1 int64 on the device. */
 int opp_segmented_mean(const float* rows, int D, const long long* offsets, int n_seg, float* out, void* stream);
 
+/* ---- SfM point cloud post-processing: what runs between COLMAP's points3D and the bank above ----------------
+ * filter_bbox and merge of src/sfm_utils/postprocess/filter_points.py (:172-234, :265-297) in float64, every
+ * operation rounded on its own (no FMA contraction).  xyz [n][3] float64 on the device, n <= 2^20.
+ *
+ * opp_pc_box_mask: mask[i] = 1 iff 0 < (p - c4) . v < v . v for v = c5 - c4, c0 - c4, c7 - c4 (strict on every
+ * face).  `corners` [8][3] is a HOST array. */
+int opp_pc_box_mask(const double* xyz, int n, const double* corners, unsigned char* mask, void* stream);
+/* The merge, in five steps the caller strings together (onepose_plus_plus_amd/pointcloud.py); nothing of size n x n
+ * is ever allocated.  N(j) = { i : sqrt(dx^2 + dy^2 + dz^2) < thr }, j itself included.
+ *   1. opp_pc_neighbor_count: counts[j] = |N(j)| (int32 [n]).
+ *   2. the caller forms offsets [n + 1] int64 = exclusive prefix sum of counts and reads pairs = offsets[n] back;
+ *      it refuses a total above its own limit here, before the lists are allocated.
+ *   3. opp_pc_neighbor_fill: N(j) in ascending index at nbr[offsets[j] .. offsets[j + 1]) inside the workspace.
+ *   4. opp_pc_select: sel[j] = 1 iff the reference's walk j = 0 .. n-1 takes row j (no earlier taken row shares a
+ *      neighbour with it); selcnt[j] = sel[j] ? |N(j)| : 0.  One workgroup iterates rounds, at most n; *status = 1
+ *      if that bound was reached with rows undecided (the results are then invalid), else 0.
+ *   5. opp_pc_emit: rank / mem_end [n] int64 = INCLUSIVE prefix sums of sel / selcnt, n_clusters / n_members their
+ *      last entries.  Cluster c = the c-th selected row: ret_points[c] = ((x_i0 + x_i1) + ...) / k over N(j) in
+ *      ascending position (numpy's axis-0 mean), members[cl_offsets[c] .. cl_offsets[c + 1]) = ids[N(j)].
+ * opp_pc_workspace_bytes is host-only; the same workspace (and `pairs`) goes to steps 3-5.  0 = arguments out of range. */
+size_t opp_pc_workspace_bytes(int n, long long pairs);
+int opp_pc_neighbor_count(const double* xyz, int n, double thr, int* counts, void* stream);
+int opp_pc_neighbor_fill(const double* xyz, int n, double thr, const long long* offsets, long long pairs, void* ws, size_t ws_bytes,
+                         void* stream);
+int opp_pc_select(const long long* offsets, int n, long long pairs, int* sel, int* selcnt, int* status, void* ws, size_t ws_bytes,
+                  void* stream);
+int opp_pc_emit(const double* xyz, const long long* ids, int n, long long pairs, const long long* offsets, const int* sel,
+                const long long* rank, const long long* mem_end, long long n_clusters, long long n_members, double* ret_points,
+                long long* cl_offsets, long long* members, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- pose from the matches (next row after the matcher) --------------------
  * PnP-RANSAC on the device: replaces ransac_PnP / cv2.solvePnPRansac(EPNP, 10000 iterations)
  * (src/utils/metric_utils.py:121-204) so the matches never leave the GPU.  pts2d [n][2] (pixels),

@@ -169,6 +169,13 @@ SIGNATURES = {
     "opp_image_ingest_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "opp_crop_warp_u8": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, POINTER(c_int), c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "opp_segmented_mean": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "opp_pc_workspace_bytes": (c_size_t, [c_int, c_longlong]),
+    "opp_pc_box_mask": (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), c_void_p, c_void_p]),
+    "opp_pc_neighbor_count": (c_int, [c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p]),
+    "opp_pc_neighbor_fill": (c_int, [c_void_p, c_int, ctypes.c_double, c_void_p, c_longlong, c_void_p, c_size_t, c_void_p]),
+    "opp_pc_select": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "opp_pc_emit": (c_int, [c_void_p, c_void_p, c_int, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_longlong,
+                            c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_debug_timestamps": (c_int, [c_void_p]),
     "opp_pnp_workspace_bytes": (c_size_t, [c_int]),
     "opp_pnp_ransac": (c_int, [c_void_p, c_void_p, c_int, POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double,

@@ -72,7 +72,7 @@ def main():
             print("%s: COMPILE FAILED\n%s" % (src, err))
             bad = 1
             continue
-        print("# %s (%d kernels)%s" % (src, len(rows), "  [-fno-slp-vectorize]" if build.SOURCE_FLAGS.get(src) else ""))
+        print("# %s (%d kernels)%s" % (src, len(rows), "  [%s]" % " ".join(build.SOURCE_FLAGS[src]) if build.SOURCE_FLAGS.get(src) else ""))
         for k, vg, ag, sc, water, mfma, pk in rows:
             short = re.sub(r"^_ZN\d+_GLOBAL__N_1", "", k)[:96]
             flag = ""
