@@ -13,6 +13,8 @@
  *    weight blob (sizes from the *_bytes queries) and owns every buffer.
  *  - every call enqueues work on `stream` (a hipStream_t passed as void*) and returns
  *    without synchronising; 0 = ok, negative = error (message via opp_last_error()).
+ *  - a workspace is never read before the call has written it, nothing is written outside workspace[0, *_workspace_bytes) and
+ *    the documented extent of each output, and a workspace that is too small is refused with -4 before anything is launched.
  *  - activations are NHWC ("pixel-major, channel contiguous"); the 196-channel stages are
  *    padded to 224 channels with zeros.
  *  - batch size is 1 (the reference's inference path, inference_OnePosePlus_worker.py:52-60).
@@ -256,7 +258,7 @@ int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W, const flo
 /* Fine level (OnePosePlusModel.py:179-201): FinePreprocess window gather, loftr_fine,
  * FineMatching.  feat_f NHWC [Hf][Wf][d_fine]; bank_f [d_fine][N] (RAW fine bank, quirk q8);
  * ids are the first M entries of the coarse outputs.  base_scale = H/Hf; query_scale as above.
- * run_transformer = config loftr_fine.enable. */
+ * run_transformer = config loftr_fine.enable.  The workspace must hold opp_fine_workspace_bytes whether run_transformer is set or not. */
 size_t opp_fine_workspace_bytes(const opp_ctx* ctx, int n_matches);
 int opp_fine(opp_ctx* ctx, const float* feat_f, int Hf, int Wf, const float* bank_f, int n_points,
              const long long* i_ids, const long long* j_ids, int n_matches, int hc, int wc,

@@ -1453,6 +1453,15 @@ extern "C" int opp_backbone(opp_ctx* ctx, const float* image, int H, int W, floa
 // ----------------------------------------------------------------------------------------
 namespace {
 
+// whether the statistics of encode_points_impl fit behind a's current offset (a dry run: a itself is left alone)
+bool encode_points_fits(const opp_ctx* c, const Arena& a) {
+  if (!c->cfg.kpt_enc_enable) return true;
+  Arena probe = a;
+  probe.f(8);
+  probe.f(8);
+  return probe.ok;
+}
+
 int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n, float* t3, Arena& a, hipStream_t s) {
   const int C = c->cfg.coarse_d_model;
   if (c->cfg.kpt_enc_enable) {
@@ -1479,6 +1488,10 @@ int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n
 int coarse_tokens_impl(opp_ctx* c, const float* feat_c, const float* pe, int L, const float* kpts, const float* bank_c,
                        int n, const float* tokens3d_pre, float* tokens, Arena& a, hipStream_t s) {
   const int C = c->cfg.coarse_d_model;
+  if (!tokens3d_pre && !encode_points_fits(c, a)) {     // refused before the image half is launched
+    opp_set_error("coarse_tokens: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
   if (pe && tokens3d_pre)      // the serving case: one launch for feat_c + pe and the cached point tokens
     return opp_add_cat(feat_c, pe, (size_t)L * C, tokens3d_pre, (size_t)n * C, tokens, s);
   if (pe) {
@@ -1548,6 +1561,15 @@ size_t plan_transformer(int C, int D, int n_seg, int len0, int len1, Arena& a, T
   b.ks = a.f((size_t)2 * n_seg * C);
   b.scratch = a.f(linattn_scratch_floats(C, D, n_seg, len0, len1));
   return a.off;
+}
+
+// whether plan_transformer fits behind a's current offset (a dry run: a itself is left alone) -- for the entries that launch other
+// work in front of their transformer and must refuse a short workspace before that
+bool transformer_fits(int C, int D, int n_seg, int len0, int len1, const Arena& a) {
+  Arena probe = a;
+  TrBufs b;
+  plan_transformer(C, D, n_seg, len0, len1, probe, b);
+  return probe.ok;
 }
 
 struct LnArgs {   // LayerNorm fused into the GEMM epilogue (output rows = whole tile rows)
@@ -1884,8 +1906,9 @@ extern "C" int opp_object_prefix(opp_ctx* ctx, const float* tokens3d, int n_poin
                 "object_prefix: prefix buffer too small or not 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   ObjPrefix pre = obj_prefix_view(static_cast<float*>(prefix), C, D, n_points);
-  OPP_TRY(copy_f(pre.x1, tokens3d, (size_t)n_points * C, s));
   Arena a(ws, ws_bytes);
+  OPP_CHECK_WS(transformer_fits(C, D, 1, 0, n_points, a), "object_prefix: workspace too small");
+  OPP_TRY(copy_f(pre.x1, tokens3d, (size_t)n_points * C, s));
   return transformer_impl(lv, pre.x1, 1, 0, n_points, a, s, gemm_prec(ctx->cfg),
                           {.fusion = ctx->cfg.encoder_fusion, .prefix_mode = OPP_PREFIX_MAKE, .pre = &pre});
 }
@@ -1976,24 +1999,40 @@ extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg
 // ----------------------------------------------------------------------------------------
 namespace {
 
+// the matcher's share of a workspace: selection scratch, (max, sum exp) partials and the pre-split operands of the configured score path
+struct MatchBufs {
+  float *scratch = nullptr, *stats = nullptr, *f2_split = nullptr, *f3_split = nullptr;
+  int sprec = OPP_PREC_FP32;
+  bool two_sweep = false;
+};
+size_t plan_coarse_match(const opp_ctx* c, int n, int L, Arena& a, MatchBufs& b) {
+  const int C = c->cfg.coarse_d_model;
+  b.scratch = a.f(opp_coarse_match_scratch_floats(n, L));
+  b.stats = a.f(opp_coarse_match_stats_floats(n, L));
+  b.sprec = score_prec(c->cfg);                // score GEMM on the split-operand path as well
+  b.f2_split = b.sprec != OPP_PREC_FP32 ? a.f(split_floats((size_t)L * C, b.sprec)) : nullptr;
+  // (the split-operand core addresses its operands and output with 32-bit offsets: beyond that the r02 path reports the limit)
+  b.two_sweep = b.sprec == OPP_PREC_BF16X3 && c->cfg.score_two_sweep && C % 32 == 0 && (size_t)n * L < (1ull << 31) &&
+                (size_t)(n > L ? n : L) * C * 6 < (1ull << 31);
+  b.f3_split = b.two_sweep ? a.f(split_floats((size_t)n * C, b.sprec)) : nullptr;
+  return a.off;
+}
+
 int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int hc, int wc, const float* kpts, float base_scale,
                       const float* qscale, float* conf, long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c,
                       float* mkpts_3d, int* count, Arena& a, hipStream_t s) {
   const int C = c->cfg.coarse_d_model, L = hc * wc;
   // coarse_matching.feat_norm_method: "sqrt_feat_dim" divides both token sets by sqrt(C), "none" leaves them (coarse_matching.py:46-50)
   const float feat_mul = c->cfg.feat_norm == 1 ? 1.0f : 1.0f / (float)C;
-  float* scratch = a.f(opp_coarse_match_scratch_floats(n, L));
-  float* stats = a.f(opp_coarse_match_stats_floats(n, L));
-  const int sprec = score_prec(c->cfg);                // score GEMM on the split-operand path as well
-  float* f2_split = sprec != OPP_PREC_FP32 ? a.f(split_floats((size_t)L * C, sprec)) : nullptr;
-  // (the split-operand core addresses its operands and output with 32-bit offsets: beyond that the r02 path reports the limit)
-  const bool two_sweep = sprec == OPP_PREC_BF16X3 && c->cfg.score_two_sweep && C % 32 == 0 && (size_t)n * L < (1ull << 31) &&
-                         (size_t)(n > L ? n : L) * C * 6 < (1ull << 31);
-  float* f3_split = two_sweep ? a.f(split_floats((size_t)n * C, sprec)) : nullptr;
+  MatchBufs mb;
+  plan_coarse_match(c, n, L, a, mb);
   if (!a.ok) {
     opp_set_error("coarse_match: workspace too small");
     return OPP_ERR_WORKSPACE;
   }
+  float *const scratch = mb.scratch, *const stats = mb.stats, *const f2_split = mb.f2_split, *const f3_split = mb.f3_split;
+  const int sprec = mb.sprec;
+  const bool two_sweep = mb.two_sweep;
   if (two_sweep) {
     // both operands pre-split once (7.7 + 6.3 MB); in the forward they are one token buffer [L + n][C] and the two split buffers are adjacent in
     // the workspace: one launch (r05)
@@ -2056,7 +2095,11 @@ int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int h
 }  // namespace
 
 extern "C" size_t opp_coarse_match_workspace_bytes(const opp_ctx* ctx, int n, int L) {
-  (void)ctx;
+  if (ctx) {   // what this context's score path plans, no more: half of it is then always too little
+    Arena a(nullptr, 0);
+    MatchBufs b;
+    return opp_align(plan_coarse_match(ctx, n, L, a, b)) + 256;
+  }
   return opp_align(opp_coarse_match_scratch_floats(n, L) * sizeof(float)) +
          opp_align(opp_coarse_match_stats_floats(n, L) * sizeof(float)) +
          opp_align((size_t)L * 256 * sizeof(float) * 3 / 2) + opp_align((size_t)n * 256 * sizeof(float) * 3 / 2) + 1024;
@@ -2165,6 +2208,18 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   const bool keep_inputs = !feat_f && ctx->fine_x1 && ctx->fine_x2o;   // opp_set_fine_patch_buffers: x1 / x2_out land in the caller's buffers
   const FineWant want = feat_f ? FineWant::Whole : (keep_inputs ? FineWant::Quarter : FineWant::None);
   const bool overlap = want != FineWant::None && ctx->cfg.fpn_overlap;
+  {   // the stages behind the backbone share what the workspace has left: all of their plans are tried before the first launch
+    Arena probe = a;
+    BackboneBufs bb;
+    plan_backbone(ctx, 1, H, W, true, probe, bb);
+    if (!overlap) probe.off = mark;                  // one stream: the later stages reuse the backbone's maps
+    const size_t rest = probe.off;
+    MatchBufs mb;
+    plan_coarse_match(ctx, n, L, probe, mb);
+    probe.off = rest;
+    OPP_CHECK_WS(probe.ok && transformer_fits(C, lv.D(), 1, L, n, probe) && (tokens3d_pre || encode_points_fits(ctx, probe)),
+                 "forward_coarse: workspace too small");
+  }
   SideBranch side{ctx, s};
   if (overlap) OPP_TRY(side.ensure());
   {
@@ -2206,6 +2261,14 @@ int fine_tail(opp_ctx* ctx, float* X, int M, const float* mkpts_c, float base_sc
   if (run_transformer) OPP_TRY(transformer_impl(level_of(ctx, 1), X, M, WW, 1, a, s, gemm_prec(ctx->cfg), {.fusion = ctx->cfg.encoder_fusion}));
   const float temp = (float)(1.0 / sqrt((double)C));   // fine_matching.py:82
   return opp_fine_head(f3, C, X, C, M, Wwin, C, temp, mkpts_c, base_scale, qscale, expec_f, mkpts_f, s);
+}
+
+// whether fine_tail's transformer fits behind a's current offset: asked before the first launch of a fine entry.  The size queries of the
+// fine entries have no run_transformer argument, so the share of loftr_fine is asked for whether this call runs it or not: what the
+// query reports is what a call needs
+bool fine_tail_fits(const opp_ctx* ctx, int M, const Arena& a) {
+  const EncLevel lv = level_of(ctx, 1);
+  return transformer_fits(lv.C, lv.D(), M, ctx->cfg.fine_window * ctx->cfg.fine_window, 1, a);
 }
 
 struct PatchBufs {
@@ -2273,6 +2336,7 @@ extern "C" int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_o
     opp_set_error("fine_patches: workspace too small");
     return OPP_ERR_WORKSPACE;
   }
+  OPP_CHECK_WS(fine_tail_fits(ctx, M, a), "fine_patches: workspace too small");
   OppProfScope prof(OPP_PROF_FINE, s, (double)M * ((double)(WW + 1) * C * 4.0 + 5 * 4.0));
   const int hp = gemm_prec(ctx->cfg);
   const int org = -(Wwin / 2);                      // window origin relative to the match's fine-map pixel (fine_preprocess.py:41-47: padding W // 2)
@@ -2345,6 +2409,7 @@ extern "C" int opp_fine(opp_ctx* ctx, const float* feat_f, int Hf, int Wf, const
     opp_set_error("fine: workspace too small");
     return OPP_ERR_WORKSPACE;
   }
+  OPP_CHECK_WS(fine_tail_fits(ctx, M, a), "fine: workspace too small");
   float* f3 = X + (size_t)M * WW * C;
   // whole fine stage as one profiled span; algorithmic bytes: windows + point descriptors gathered, outputs written
   OppProfScope prof(OPP_PROF_FINE, s, (double)M * ((double)(WW + 1) * C * 4.0 + 5 * 4.0));
@@ -2396,7 +2461,8 @@ extern "C" int opp_pack_conv_weight(const float* w, const float* scale, int cout
 // ----------------------------------------------------------------------------------------
 // training loss
 // ----------------------------------------------------------------------------------------
-extern "C" size_t opp_focal_loss_workspace_bytes(size_t n) { return opp_focal_loss_ws_bytes(n) + 256; }
+// exactly the block partials: with slack on top, half of the reported size was enough for a single block and was accepted
+extern "C" size_t opp_focal_loss_workspace_bytes(size_t n) { return opp_focal_loss_ws_bytes(n); }
 
 extern "C" int opp_focal_loss_forward(const float* conf, const short* conf_gt, const float* weight, size_t n, float alpha,
                                       float gamma, double* sums, void* ws, size_t ws_bytes, void* stream) {
@@ -2581,7 +2647,7 @@ extern "C" int opp_conv2d_backward_nhwc(const float* x, int B, int Hin, int Win,
   Arena a(ws, ws_bytes);
   ConvBwdWs cw;
   conv_bwd_alloc(a, n, cw);
-  OPP_CHECK_ARG(a.ok, "conv2d_backward: workspace too small");
+  OPP_CHECK_WS(a.ok, "conv2d_backward: workspace too small");
   return conv_backward(x, B, Hin, Win, cin, w, cout, ks, stride, grad_y, grad_x, grad_x_add, grad_w, prec, cw, (hipStream_t)stream);
 }
 
@@ -2590,7 +2656,7 @@ extern "C" size_t opp_batchnorm_backward_workspace_bytes(int rows, int ld) { ret
 extern "C" int opp_batchnorm_backward_nhwc(const float* grad_y, const float* y, const float* raw, int rows, int ld, int C, int act, const float* gamma,
                                            const float* mean, const float* invstd, float* grad_raw, float* grad_res, float* grad_gamma,
                                            float* grad_beta, void* ws, size_t ws_bytes, void* stream) {
-  OPP_CHECK_ARG(ws && ws_bytes >= opp_bn_bwd_scratch_bytes(rows, ld), "batchnorm_backward: workspace too small");
+  OPP_CHECK_WS(ws && ws_bytes >= opp_bn_bwd_scratch_bytes(rows, ld), "batchnorm_backward: workspace too small");
   return opp_bn_backward(grad_y, y, raw, rows, ld, C, act, gamma, mean, invstd, grad_raw, grad_res, grad_gamma, grad_beta, 0, ws, (hipStream_t)stream);
 }
 

@@ -627,7 +627,7 @@ int opp_conv_wgrad(const float* dY, int ldy, const float* X, int ldx, size_t x_p
   a.n_ci_tiles = opp_cdiv(cin, 128);
   const int T = ks * ks * a.n_ci_tiles * a.n_co_tiles;
   plan_splits(T, opp_cdiv(P, 32), a.splits, a.chunks_per_split);
-  OPP_CHECK_ARG(ws_bytes >= (size_t)a.splits * T * 16384 * sizeof(float), "conv_wgrad: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= (size_t)a.splits * T * 16384 * sizeof(float), "conv_wgrad: workspace too small");
   a.part = static_cast<float*>(ws);
   a.dy_bytes = (unsigned)((size_t)P * ldy * 4);
   a.x_bytes = (unsigned)(x_pixels * ldx * 4);

@@ -572,16 +572,17 @@ int opp_fullattn_train_bwd(const float* q, const float* k, const float* v, const
   OPP_CHECK_ARG(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(go) && aligned16(gq) && aligned16(gk) && aligned16(gv),
                 "full_attention_train_backward: operands must be 16-byte aligned");
   const float scale2 = kLog2e / sqrtf((float)D), sc = 1.f / sqrtf((float)D);
+  // asked of every supported shape, as the size query reports it (the vector kernels of the short streams leave it untouched)
+  if (!ws || ws_bytes < opp_fullattn_train_ws_bytes(B, L, S, H, D) || !aligned16(ws)) {
+    opp_set_error("full_attention_train_backward: workspace too small");
+    return OPP_ERR_WORKSPACE;
+  }
   if (fam == FAM_SMALL) {
     const dim3 grid(B, H);
     if (D == 16) hipLaunchKernelGGL((fat_small_bwd_kernel<16>), grid, dim3(256), 0, stream, q, k, v, lse, go, L, S, H, scale2, sc, gq, gk, gv);
     else hipLaunchKernelGGL((fat_small_bwd_kernel<32>), grid, dim3(256), 0, stream, q, k, v, lse, go, L, S, H, scale2, sc, gq, gk, gv);
     OPP_CHECK_LAUNCH("fat_small_bwd_kernel");
     return OPP_OK;
-  }
-  if (!ws || ws_bytes < opp_fullattn_train_ws_bytes(B, L, S, H, D) || !aligned16(ws)) {
-    opp_set_error("full_attention_train_backward: workspace too small");
-    return OPP_ERR_WORKSPACE;
   }
   float* delta = reinterpret_cast<float*>(ws);
   const size_t n = (size_t)B * L * H;

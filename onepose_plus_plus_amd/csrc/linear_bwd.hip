@@ -98,7 +98,7 @@ int opp_linear_bwd(const float* dY, const float* X, const float* W, int M, int N
   OPP_CHECK_ARG(N % 32 == 0 && K % 32 == 0, "linear_backward: feature counts must be multiples of 32 (got N %d, K %d)", N, K);
   OPP_CHECK_ARG((!dX || W) && (!dW || X), "linear_backward: dX needs W, dW needs X");
   const Plan p = make_plan(M, N, K, prec);
-  OPP_CHECK_ARG(ws_bytes >= p.total * sizeof(float), "linear_backward: workspace too small (%zu < %zu)", ws_bytes, p.total * sizeof(float));
+  OPP_CHECK_WS(ws_bytes >= p.total * sizeof(float), "linear_backward: workspace too small (%zu < %zu)", ws_bytes, p.total * sizeof(float));
   float* base = static_cast<float*>(ws);
   const bool b3 = prec == OPP_PREC_BF16X3;
   if (dX) {   // dX = dY W : the "weight" operand of the GEMM is W^T [K][N]

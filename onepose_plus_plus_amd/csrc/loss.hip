@@ -314,7 +314,7 @@ int opp_focal_loss_fwd_ex(const float* conf, const void* gt, int gt_kind, const 
   OPP_TRY(focal_check(conf, gt, gt_kind, weight, mask0, mask1, N, L, n, fw, vec_ok));
   OPP_CHECK_ARG(sums && ws, "focal_loss: null output");
   const int blocks = loss_blocks(n);
-  OPP_CHECK_ARG(ws_bytes >= (size_t)blocks * 4 * sizeof(double), "focal_loss: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= (size_t)blocks * 4 * sizeof(double), "focal_loss: workspace too small");
   double* part = static_cast<double*>(ws);
   {
     const double gt_b = gt_kind == 0 ? 2.0 : (gt_kind == 1 ? 4.0 : 1.0);
@@ -386,7 +386,7 @@ int opp_dual_softmax_bwd(const float* g, const float* sim, const float* lse_row,
                          float* ds, void* ws, size_t ws_bytes, hipStream_t stream) {
   OPP_CHECK_ARG(g && sim && lse_row && lse_col && ds && ws && B > 0 && N > 0 && L > 0, "dual_softmax backward: null argument / empty input");
   const DsmPlan p = dsm_plan(B, N, L);
-  OPP_CHECK_ARG(ws_bytes >= p.total * sizeof(float), "dual_softmax backward: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= p.total * sizeof(float), "dual_softmax backward: workspace too small");
   OPP_CHECK_ARG(p.vec == 1 || (aligned16(g) && aligned16(sim)), "dual_softmax backward: operands must be 16-byte aligned");
   OPP_CHECK_ARG(B <= 65535 && p.col_tiles <= 65535, "dual_softmax backward: grid too large");
   float* rpart = static_cast<float*>(ws);

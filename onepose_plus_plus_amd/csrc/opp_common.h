@@ -22,6 +22,15 @@ void opp_set_error(const char* fmt, ...);
     }                                             \
   } while (0)
 
+// a caller's workspace that is too small: refused with its own code, before the first launch of the call ("The workspace contract")
+#define OPP_CHECK_WS(cond, ...)                   \
+  do {                                            \
+    if (!(cond)) {                                \
+      opp_set_error(__VA_ARGS__);                 \
+      return OPP_ERR_WORKSPACE;                   \
+    }                                             \
+  } while (0)
+
 #define OPP_CHECK_LAUNCH(name)                                              \
   do {                                                                      \
     hipError_t e__ = hipGetLastError();                                     \

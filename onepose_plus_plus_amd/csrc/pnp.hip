@@ -168,7 +168,7 @@ extern "C" int opp_pnp_ransac(const float* pts2d, const float* pts3d, int n_poin
                               int* inlier_mask, int* n_inliers, int* ok, void* ws, size_t ws_bytes, void* stream_) {
   OPP_TRY(opp_pnp_check_args("pnp", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px, scale > 0,
                              1.0));
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_workspace_bytes(iterations), "pnp: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_pnp_workspace_bytes(iterations), "pnp: workspace too small");
   // solver 0 over every hypothesis: no stop stage, no optional output
   pnp_launch((hipStream_t)stream_, pts2d, pts3d, pnp_params(K4, reproj_error_px, scale, n_points, iterations, seed),
              pnp_carve(ws, iterations, n_points), 0, false, 1.0, refine_iters, pose_out, inlier_mask, n_inliers, ok, nullptr, nullptr, nullptr);
@@ -183,7 +183,7 @@ extern "C" int opp_pnp_ransac_ex(const float* pts2d, const float* pts3d, int n_p
   OPP_TRY(opp_pnp_check_args("pnp_ex", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
                              scale > 0, confidence));
   OPP_TRY(opp_pnp_check_solver("pnp_ex", solver));
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_ex_workspace_bytes(iterations, n_points), "pnp_ex: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_pnp_ex_workspace_bytes(iterations, n_points), "pnp_ex: workspace too small");
   if (!pnp_launch((hipStream_t)stream_, pts2d, pts3d, pnp_params(K4, reproj_error_px, scale, n_points, iterations, seed),
                   pnp_carve(ws, iterations, n_points), solver, true, confidence, refine_iters, pose_out, inlier_mask, n_inliers, ok, stop_out,
                   samples_out, scores_out)) {

@@ -158,7 +158,7 @@ extern "C" int opp_pnp_ransac_batch(const float* pts2d, const float* pts3d, cons
   OPP_TRY(opp_pnp_check_args("pnp_batch", pts2d, pts3d, n_total, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
                              scale > 0, confidence));
   OPP_TRY(opp_pnp_check_solver("pnp_batch", solver));
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_batch: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_pnp_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_batch: workspace too small");
   PnpBatch a;
   a.p2 = pts2d;
   a.p3 = pts3d;

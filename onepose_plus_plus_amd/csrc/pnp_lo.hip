@@ -73,7 +73,7 @@ extern "C" int opp_pnp_loransac(const float* pts2d, const float* pts3d, int n_po
   OPP_TRY(opp_pnp_check_args("pnp_loransac", pts2d, pts3d, n_points, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations, reproj_error_px,
                              min_trials >= 0 && min_inlier_ratio >= 0.0, confidence));
   OPP_CHECK_ARG(K4[0] > 0.0 && K4[1] > 0.0, "pnp_loransac: focal lengths must be positive");
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_loransac_workspace_bytes(iterations, n_points), "pnp_loransac: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_pnp_loransac_workspace_bytes(iterations, n_points), "pnp_loransac: workspace too small");
   LoParams prm;
   for (int k = 0; k < 4; ++k) prm.K4[k] = K4[k];
   prm.thr2 = reproj_error_px * reproj_error_px;

@@ -133,7 +133,7 @@ extern "C" int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, co
   OPP_TRY(opp_pnp_check_batch("pnp_loransac_batch", n_samples, offsets, seeds, stop));
   OPP_TRY(opp_pnp_check_args("pnp_loransac_batch", pts2d, pts3d, n_total, K4, pose_out, inlier_mask, n_inliers, ok, ws, iterations,
                              reproj_error_px, min_trials >= 0 && min_inlier_ratio >= 0.0, confidence));
-  OPP_CHECK_ARG(ws_bytes >= opp_pnp_loransac_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_loransac_batch: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_pnp_loransac_batch_workspace_bytes(iterations, n_samples, n_total), "pnp_loransac_batch: workspace too small");
   LoBatch a;
   a.p2 = pts2d;
   a.p3 = pts3d;

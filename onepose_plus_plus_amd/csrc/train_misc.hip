@@ -257,7 +257,7 @@ size_t opp_ln_backward_ws_bytes(int rows, int C) { return opp_align((size_t)opp_
 int opp_ln_backward(const float* g, const float* x, const float* gamma, const float* mean, const float* rstd, int rows, int C, float* dx,
                     float* dgamma, float* dbeta, void* ws, size_t ws_bytes, hipStream_t stream) {
   OPP_CHECK_ARG(g && x && gamma && mean && rstd && dx && dgamma && dbeta && ws && rows > 0, "layer_norm_train_backward: null / empty argument");
-  OPP_CHECK_ARG(ws_bytes >= opp_ln_backward_ws_bytes(rows, C), "layer_norm_train_backward: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_ln_backward_ws_bytes(rows, C), "layer_norm_train_backward: workspace too small");
   const int blocks = opp_cdiv(rows, 4 * kLnRowsPerWave);
   float* part = static_cast<float*>(ws);
   if (C == 256) hipLaunchKernelGGL(ln_bwd_kernel<4>, dim3(blocks), dim3(256), 0, stream, g, x, gamma, mean, rstd, rows, dx, part);
@@ -278,7 +278,7 @@ size_t opp_lse_ws_bytes(int B, int N, int L) { return opp_align((size_t)B * opp_
 int opp_dual_softmax_lse(const float* S, int B, int N, int L, float* lse_row, float* lse_col, float* conf, void* ws, size_t ws_bytes,
                          hipStream_t stream) {
   OPP_CHECK_ARG(S && lse_row && lse_col && ws && B > 0 && N > 0 && L > 0, "dual_softmax_forward: null / empty argument");
-  OPP_CHECK_ARG(ws_bytes >= opp_lse_ws_bytes(B, N, L), "dual_softmax_forward: workspace too small");
+  OPP_CHECK_WS(ws_bytes >= opp_lse_ws_bytes(B, N, L), "dual_softmax_forward: workspace too small");
   OPP_CHECK_ARG(!conf || L % 4 == 0, "dual_softmax_forward: L must be a multiple of 4");
   const long long rows = (long long)B * N;
   const int chunks = opp_cdiv(N, kLseRows);

@@ -50,8 +50,7 @@ def _rel(a, b):
     (2, 128, 196, 3, 2, 32, 48),      # layer2.0.conv1
 ])
 def test_conv2d_backward_vs_autograd(B, cin, cout, ks, stride, H, W, prec):
-    from onepose_plus_plus_amd import _lib
-    lib = _lib.load()
+    from tests import hip_ops as ops
     g = torch.Generator().manual_seed(B * 1000 + cin + cout + ks + stride)
     x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cout, cin, ks, ks, generator=g) / (cin * ks * ks) ** 0.5
@@ -61,36 +60,23 @@ def test_conv2d_backward_vs_autograd(B, cin, cout, ks, stride, H, W, prec):
     y.backward(gy.double())
     cin_p, cout_p = _pad32(cin), _pad32(cout)
     xn, gyn, wdev = _nhwc(x, cin_p), _nhwc(gy, cout_p), w.cuda().contiguous()
-    gx = torch.full((B, H, W, cin_p), float("nan"), device="cuda")
-    gw = torch.full((cout, cin, ks, ks), float("nan"), device="cuda")
-    nb = lib.opp_conv2d_backward_workspace_bytes(B, H, W, cin, cout, ks, stride, prec)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_conv2d_backward_nhwc(xn.data_ptr(), B, H, W, cin, wdev.data_ptr(), cout, ks, stride, gyn.data_ptr(), gx.data_ptr(), None,
-                                            gw.data_ptr(), prec, ws.data_ptr(), nb, _s()), "opp_conv2d_backward_nhwc")
-    torch.cuda.synchronize()
+    gx, gw = ops.conv2d_backward(xn, wdev, gyn, cin, cout, ks, stride, prec)
     assert _rel(_from_nhwc(gx, cin), xd.grad) < 5e-6, "grad_x"
     # accumulation into a buffer that already holds another consumer's gradient (aliased, as the residual blocks use it)
     add = torch.randn(B, H, W, cin_p, generator=g)
     add[..., cin:] = 0
-    acc = add.cuda().contiguous()
-    _lib.check(lib.opp_conv2d_backward_nhwc(xn.data_ptr(), B, H, W, cin, wdev.data_ptr(), cout, ks, stride, gyn.data_ptr(), acc.data_ptr(), acc.data_ptr(),
-                                            None, prec, ws.data_ptr(), nb, _s()), "opp_conv2d_backward_nhwc")
-    torch.cuda.synchronize()
+    acc, _ = ops.conv2d_backward(xn, wdev, gyn, cin, cout, ks, stride, prec, want_dw=False, add=add)
     assert _rel(_from_nhwc(acc, cin), xd.grad + add[..., :cin].permute(0, 3, 1, 2).double()) < 5e-6, "grad_x + add (aliased)"
     assert (gx[..., cin:] == 0).all(), "padded channels of grad_x must be exact zeros"
     assert _rel(gw.cpu(), wd.grad) < 5e-6, "grad_w"
     # deterministic: fixed-order split reduction
-    gw2 = torch.empty_like(gw)
-    _lib.check(lib.opp_conv2d_backward_nhwc(xn.data_ptr(), B, H, W, cin, wdev.data_ptr(), cout, ks, stride, gyn.data_ptr(), None, None,
-                                            gw2.data_ptr(), prec, ws.data_ptr(), nb, _s()), "opp_conv2d_backward_nhwc")
-    torch.cuda.synchronize()
+    _, gw2 = ops.conv2d_backward(xn, wdev, gyn, cin, cout, ks, stride, prec, want_dx=False)
     assert torch.equal(gw, gw2)
 
 
 def test_conv_wgrad_long_reduction():
     """the reduction length of the real step (tens of thousands of pixels per split chain) keeps fp32-level accuracy"""
-    from onepose_plus_plus_amd import _lib
-    lib = _lib.load()
+    from tests import hip_ops as ops
     B, cin, cout, H, W = 2, 64, 64, 96, 128
     g = torch.Generator().manual_seed(5)
     x = torch.randn(B, cin, H, W, generator=g)
@@ -99,13 +85,7 @@ def test_conv_wgrad_long_reduction():
     xd, wd = x.double(), w.double().requires_grad_(True)
     F.conv2d(xd, wd, None, 1, 1).backward(gy.double())
     xn, gyn = _nhwc(x, cin), _nhwc(gy, cout)
-    gw = torch.empty((cout, cin, 3, 3), device="cuda")
-    nb = lib.opp_conv2d_backward_workspace_bytes(B, H, W, cin, cout, 3, 1, 2)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    wdev = w.cuda()
-    _lib.check(lib.opp_conv2d_backward_nhwc(xn.data_ptr(), B, H, W, cin, wdev.data_ptr(), cout, 3, 1, gyn.data_ptr(), None, None, gw.data_ptr(), 2,
-                                            ws.data_ptr(), nb, _s()), "opp_conv2d_backward_nhwc")
-    torch.cuda.synchronize()
+    _, gw = ops.conv2d_backward(xn, w.cuda(), gyn, cin, cout, 3, 1, 2, want_dx=False)
     # error relative to sum |a||b| ~ sqrt(P) * 0.64: a few fp32 ulps of the largest partial sums
     err = float((gw.cpu().double() - wd.grad).abs().max())
     assert err < 5e-6 * (B * H * W) ** 0.5, err
@@ -114,8 +94,7 @@ def test_conv_wgrad_long_reduction():
 @pytest.mark.parametrize("act", [0, 1, 2])
 @pytest.mark.parametrize("rows,C,with_res", [(700, 128, True), (513, 196, False), (64, 256, True)])
 def test_batchnorm_backward_vs_autograd(rows, C, act, with_res):
-    from onepose_plus_plus_amd import _lib
-    lib = _lib.load()
+    from tests import hip_ops as ops
     ld = _pad32(C)
     g = torch.Generator().manual_seed(rows + C + act)
     raw = torch.randn(rows, C, generator=g) * 2 + 0.5
@@ -141,15 +120,7 @@ def test_batchnorm_backward_vs_autograd(rows, C, act, with_res):
     pi[:C] = (1.0 / torch.sqrt(var.detach() + 1e-5)).float()
     gyn, yn, rawn = padded(gy), padded(y.detach().float()), padded(raw)
     gam_d, pm_d, pi_d = gamma.cuda(), pm.cuda(), pi.cuda()          # named: a temporary's pointer would dangle once the expression ends
-    d_raw = torch.full((rows, ld), float("nan"), device="cuda")
-    d_res = torch.full((rows, ld), float("nan"), device="cuda")
-    dg, db = torch.empty(C, device="cuda"), torch.empty(C, device="cuda")
-    nb = lib.opp_batchnorm_backward_workspace_bytes(rows, ld)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_batchnorm_backward_nhwc(gyn.data_ptr(), yn.data_ptr(), rawn.data_ptr(), rows, ld, C, act, gam_d.data_ptr(),
-                                               pm_d.data_ptr(), pi_d.data_ptr(), d_raw.data_ptr(), d_res.data_ptr(), dg.data_ptr(),
-                                               db.data_ptr(), ws.data_ptr(), nb, _s()), "opp_batchnorm_backward_nhwc")
-    torch.cuda.synchronize()
+    d_raw, d_res, dg, db = ops.batchnorm_backward(gyn, yn, rawn, C, act, gam_d, pm_d, pi_d)
     assert _rel(d_raw[:, :C].cpu(), rd.grad) < 1e-5
     assert (d_raw[:, C:] == 0).all()
     assert _rel(dg.cpu(), gd.grad) < 1e-5 and _rel(db.cpu(), bd.grad) < 1e-5
@@ -195,20 +166,12 @@ def test_layer_norm_node_vs_autograd(rows, C):
 
 @pytest.mark.parametrize("B,N,L", [(2, 150, 96), (1, 333, 260), (3, 17, 8)])
 def test_dual_softmax_forward_lse_and_conf(B, N, L):
-    from onepose_plus_plus_amd import _lib
-    lib = _lib.load()
+    from tests import hip_ops as ops
     g = torch.Generator().manual_seed(N)
     S = torch.randn(B, N, L, generator=g) * 4
     S[0, :, :2] -= 1e9                                      # masked cells
     Sd = S.double()
-    Sc = S.cuda()
-    lr, lc = torch.empty(B, N, device="cuda"), torch.empty(B, L, device="cuda")
-    conf = torch.empty(B, N, L, device="cuda")
-    nb = lib.opp_dual_softmax_forward_workspace_bytes(B, N, L)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_dual_softmax_forward(Sc.data_ptr(), B, N, L, lr.data_ptr(), lc.data_ptr(), conf.data_ptr() if L % 4 == 0 else None,
-                                            ws.data_ptr(), nb, _s()), "opp_dual_softmax_forward")
-    torch.cuda.synchronize()
+    lr, lc, conf = ops.dual_softmax_forward(S, with_conf=L % 4 == 0)
     for got, want in ((lr, torch.logsumexp(Sd, 2)), (lc, torch.logsumexp(Sd, 1))):
         assert float(((got.cpu().double() - want).abs() / want.abs().clamp(min=1)).max()) < 2e-6
     if L % 4 == 0:
@@ -377,25 +340,16 @@ def test_backbone_node_vs_autograd(precision):
 @pytest.mark.parametrize("M,N,K", [(9096, 768, 256), (1000, 256, 512), (77, 128, 128)])
 def test_linear_weight_gradient_on_the_pixel_major_kernel(M, N, K):
     """opp_linear_backward (bf16x3) now forms dW on conv_wgrad_kernel straight from the token-major operands"""
-    from onepose_plus_plus_amd import _lib
-    lib = _lib.load()
+    from tests import hip_ops as ops
     g = torch.Generator().manual_seed(M)
     x, gy, w = torch.randn(M, K, generator=g), torch.randn(M, N, generator=g), torch.randn(N, K, generator=g)
     want_w = gy.double().t() @ x.double()
     want_x = gy.double() @ w.double()
     xc, gc, wc = x.cuda(), gy.cuda(), w.cuda()
-    dx, dw = torch.empty(M, K, device="cuda"), torch.empty(N, K, device="cuda")
-    nb = lib.opp_linear_backward_workspace_bytes(M, N, K, 2)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-    _lib.check(lib.opp_linear_backward(gc.data_ptr(), xc.data_ptr(), wc.data_ptr(), M, N, K, dx.data_ptr(), dw.data_ptr(), 0, 2, ws.data_ptr(), nb, _s()),
-               "opp_linear_backward")
-    torch.cuda.synchronize()
+    dx, dw = ops.linear_backward(gc, xc, wc, 2)
     assert float((dw.cpu().double() - want_w).abs().max()) < 3e-6 * M ** 0.5
     assert float((dx.cpu().double() - want_x).abs().max()) < 1e-6 * N
-    dw2 = dw.clone()
-    _lib.check(lib.opp_linear_backward(gc.data_ptr(), xc.data_ptr(), wc.data_ptr(), M, N, K, None, dw2.data_ptr(), 1, 2, ws.data_ptr(), nb, _s()),
-               "opp_linear_backward")
-    torch.cuda.synchronize()
+    _, dw2 = ops.linear_backward(gc, xc, wc, 2, want_dx=False, dw_into=dw)
     assert float((dw2.cpu().double() - 2 * want_w).abs().max()) < 6e-6 * M ** 0.5      # accumulate_grad_w
 
 
