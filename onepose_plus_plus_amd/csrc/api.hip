@@ -220,10 +220,15 @@ void mk_transformer(opp_ctx* c, const std::string& name, int d, int n_layers, bo
   }
 }
 
-// bump allocator over a caller-provided buffer
+// Bump allocator over a caller-provided buffer.  Every entry that takes (ws, ws_bytes) follows one pattern -- plan, check, run on bufs:
+//   * a plan_* function lays every buffer of the whole call, those of the stages it runs included, out into a bufs struct.  Stages that
+//     use the same bytes one after another are planned from the same mark (mark / rewind); `peak` is the most the call ever holds;
+//   * the size query is that plan on a null arena: opp_align(peak) + the query's constant margin;
+//   * the entry runs the plan on the caller's buffer behind its argument checks and refuses (OPP_CHECK_WS(a.ok, ..)) before anything is
+//     enqueued; the functions that launch take the bufs struct and never see an arena.
 struct Arena {
   char* base;
-  size_t cap, off = 0;
+  size_t cap, off = 0, peak = 0;
   bool ok = true;
   Arena(void* b, size_t c) : base((char*)b), cap(c) {}
   float* f(size_t n) { return (float*)raw(n * sizeof(float)); }
@@ -234,8 +239,11 @@ struct Arena {
       return base;
     }
     off = o + bytes;
+    peak = off > peak ? off : peak;
     return base ? base + o : nullptr;
   }
+  size_t mark() const { return off; }
+  void rewind(size_t m) { off = m; }
 };
 
 }  // namespace
@@ -831,7 +839,7 @@ size_t plan_backbone(const opp_ctx* c, int B, int H, int W, bool infer, Arena& a
   b.x2o = a.f(p4 * c2);
   b.l1 = a.f(p2 * c2);
   b.u1 = a.f(p2 * c2);
-  if (!infer) return a.off;
+  if (!infer) return a.peak;
   b.sk1 = a.f(kSplitKScratchFloats);
   b.sk2 = a.f(kSplitKScratchFloats);
   if (gemm_prec(c->cfg) == OPP_PREC_BF16X3 && asp_env_on()) {
@@ -846,7 +854,7 @@ size_t plan_backbone(const opp_ctx* c, int B, int H, int W, bool infer, Arena& a
     b.l2s = a.raw(p4 * split_row_bytes(c3));
     b.u2s = a.raw(p4 * split_row_bytes(c3));
   }
-  return a.off;
+  return a.peak;
 }
 
 // The stem as a GEMM over its im2col rows (opp_stem_im2col: [M][64], 49 taps + zero padding): C [M][pad32(cout)] = act(col * w^T + bias).
@@ -891,22 +899,11 @@ float* fp32_of(float* buf, void* tw, int hp, std::initializer_list<const ConvDes
 
 // The eval-mode ResNetFPN_8_2.forward as three stages over one planned BackboneBufs: the trunk (stem .. layer3_outconv -> feat_c; the coarse
 // level needs nothing else), the FPN fine branch at 1/4 (x2, feat_c -> x2_out) and at 1/2 resolution (x1, x2_out -> feat_f).  An entry call takes
-// one AspScope around them and prepares once, before any launch; the trunk's twin decisions (b.x1s, b.x2s) reach the fine stages through b.
+// one AspScope around them and plans once, before any launch; the trunk's twin decisions (b.x1s, b.x2s) reach the fine stages through b.
 int backbone_checks(const opp_ctx* c, int H, int W) {
   OPP_CHECK_ARG(c && c->packed, "backbone: weights not packed");
   OPP_CHECK_ARG(c->bn_packed, "backbone: weights were packed with scope 1 (training step: no BatchNorm-folded convolutions); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone: H,W must be multiples of 8 (got %dx%d)", H, W);
-  return OPP_OK;
-}
-int backbone_prepare(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& b, float* x1_ext = nullptr, float* x2o_ext = nullptr) {
-  OPP_TRY(backbone_checks(c, H, W));
-  plan_backbone(c, 1, H, W, true, a, b);
-  if (!a.ok) {
-    opp_set_error("backbone: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  if (x1_ext) b.x1 = x1_ext;       // caller-owned buffers receive x1 / x2_out instead of the workspace (match-driven fine branch)
-  if (x2o_ext) b.x2o = x2o_ext;
   return OPP_OK;
 }
 int backbone_trunk(const opp_ctx* c, const float* image, int H, int W, float* feat_c, BackboneBufs& b, hipStream_t s) {
@@ -972,7 +969,7 @@ size_t plan_fine_branch(const opp_ctx* c, int H, int W, Arena& a, BackboneBufs& 
   b.l1 = a.f(p2 * pad32(c->cfg.block_dims[1]));
   b.u1 = a.f(p2 * pad32(c->cfg.block_dims[1]));
   b.sk2 = a.f(kSplitKScratchFloats);      // small images: these convolutions run as K slices, as inside the one-call path
-  return a.off;
+  return a.peak;
 }
 
 }  // namespace
@@ -1014,7 +1011,7 @@ size_t plan_tape(const opp_ctx* c, int B, int H, int W, Arena& a, Tape& t) {
   t.raw_u1 = a.f(p2 * c2);
   t.u1 = a.f(p2 * c2);
   t.stats = a.f(c->bn_names.size() * 512);
-  return a.off;
+  return a.peak;
 }
 
 // What backbone_train_walk writes: a Tape, whose slots may alias each other where nothing reads them later, and what the walk needs beside it
@@ -1032,7 +1029,7 @@ size_t plan_tape_ws(const opp_ctx* c, int B, int H, int W, Arena& a, TrainBufs& 
   float* dsbuf = a.f(p4 * pad32(c->cfg.block_dims[2] > c->cfg.block_dims[1] ? c->cfg.block_dims[2] : c->cfg.block_dims[1]));
   for (float*& d : v.ds) d = dsbuf;
   v.bn_scratch = a.raw(opp_bn_train_scratch_bytes((int)p2, 256));
-  return a.off;
+  return a.peak;
 }
 
 // workspace of opp_backbone_train, which keeps nothing: the maps of the eval-mode walk (two ping-pong maps per resolution) and ONE buffer
@@ -1062,7 +1059,7 @@ size_t plan_backbone_train(const opp_ctx* c, int B, int H, int W, Arena& a, Trai
   t.l1 = b.l1;
   t.u1 = b.u1;
   t.stats = nullptr;
-  return a.off;
+  return a.peak;
 }
 
 // ResNetFPN_8_2.forward in train() mode (BatchNorm batch statistics), B images per call: both training entries.  Every raw convolution
@@ -1143,7 +1140,7 @@ void conv_bwd_need(ConvBwdNeed& n, int B, int Hin, int Win, int cin, int cout, i
     mx(n.wg, opp_conv_wgrad_ws_bytes(B * Ho * Wo, pad32(cout), pad32(cin), ks));
   }
 }
-void conv_bwd_alloc(Arena& a, const ConvBwdNeed& n, ConvBwdWs& w) {
+size_t plan_conv_bwd(const ConvBwdNeed& n, Arena& a, ConvBwdWs& w) {
   w.wt_tmp = a.f(n.wt_tmp);
   w.wt_pack = a.f(n.wt_pack);
   w.wt_split = a.f(n.wt_split);
@@ -1152,6 +1149,7 @@ void conv_bwd_alloc(Arena& a, const ConvBwdNeed& n, ConvBwdWs& w) {
   w.geo = a.raw(n.geo);
   w.wg = a.raw(n.wg);
   w.wg_bytes = n.wg;
+  return a.peak;
 }
 
 // x [B][Hin][Win][pad32(cin)], w [cout][cin][ks][ks] (PyTorch), dy [B][Ho][Wo][pad32(cout)] (padded channels zero).
@@ -1274,18 +1272,11 @@ size_t plan_backbone_bwd(const opp_ctx* c, int B, int H, int W, Arena& a, BwdBuf
   conv_bwd_need(n, B, H2, W2, d1, c->l1_out.cout, 1, 1, true, true, prec);
   conv_bwd_need(n, B, H2, W2, c->l1_out2a.cin, c->l1_out2a.cout, 3, 1, true, true, prec);
   conv_bwd_need(n, B, H2, W2, c->l1_out2b.cin, c->l1_out2b.cout, 3, 1, true, true, prec);
-  conv_bwd_alloc(a, n, b.cw);
-  return a.off;
+  return plan_conv_bwd(n, a, b.cw);
 }
 
 int backbone_backward_impl(opp_ctx* c, const float* image, int B, int H, int W, const Tape& t, const float* const* w, const float* dfc,
-                           const float* dff, float* const* grads, Arena& a, hipStream_t s) {
-  BwdBufs b;
-  plan_backbone_bwd(c, B, H, W, a, b);
-  if (!a.ok) {
-    opp_set_error("backbone_backward: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+                           const float* dff, float* const* grads, const BwdBufs& b, hipStream_t s) {
   const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4, H8 = H / 8, W8 = W / 8;
   const int prec = gemm_prec(c->cfg);
   const float *x1 = t.blk[1].y, *x2 = t.blk[3].y, *x3 = t.blk[5].y;
@@ -1370,10 +1361,7 @@ extern "C" int opp_backbone_train_tape(opp_ctx* ctx, const float* image, int B, 
   OPP_CHECK_ARG(B > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_train_tape: bad B / H / W (%d, %dx%d)", B, H, W);
   Arena a(ws, ws_bytes);
   plan_tape_ws(ctx, B, H, W, a, v);
-  if (!a.ok) {
-    opp_set_error("backbone_train_tape: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+  OPP_CHECK_WS(a.ok, "backbone_train_tape: workspace too small");
   return backbone_train_walk(ctx, image, B, H, W, feat_c, feat_f, bn_stats, v, (hipStream_t)stream);
 }
 
@@ -1393,10 +1381,7 @@ extern "C" int opp_backbone_train(opp_ctx* ctx, const float* image, int B, int H
   Arena a(ws, ws_bytes);
   TrainBufs v;
   plan_backbone_train(ctx, B, H, W, a, v);
-  if (!a.ok) {
-    opp_set_error("backbone_train: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+  OPP_CHECK_WS(a.ok, "backbone_train: workspace too small");
   return backbone_train_walk(ctx, image, B, H, W, feat_c, feat_f, bn_stats, v, (hipStream_t)stream);
 }
 
@@ -1426,7 +1411,10 @@ extern "C" int opp_backbone_backward(opp_ctx* ctx, const float* image, int B, in
     if (d->bn_idx >= 0) OPP_CHECK_ARG(grads[d->bn_idx] && grads[d->bn_idx + 1], "backbone_backward: BatchNorm gradient pointer %d is null", d->bn_idx);
   }
   Arena a(ws, ws_bytes);
-  return backbone_backward_impl(ctx, image, B, H, W, t, weights, grad_feat_c, grad_feat_f, grads, a, (hipStream_t)stream);
+  BwdBufs b;
+  plan_backbone_bwd(ctx, B, H, W, a, b);
+  OPP_CHECK_WS(a.ok, "backbone_backward: workspace too small");
+  return backbone_backward_impl(ctx, image, B, H, W, t, weights, grad_feat_c, grad_feat_f, grads, b, (hipStream_t)stream);
 }
 
 extern "C" size_t opp_backbone_workspace_bytes(const opp_ctx* ctx, int H, int W) {
@@ -1440,10 +1428,12 @@ extern "C" int opp_backbone(opp_ctx* ctx, const float* image, int H, int W, floa
                             size_t ws_bytes, void* stream) {
   FlagScope flag_scope(ctx);
   OPP_CHECK_ARG(ctx && image && feat_c && feat_f && ws, "backbone: null argument");
+  OPP_TRY(backbone_checks(ctx, H, W));
   Arena a(ws, ws_bytes);
   AspScope asp_scope;
   BackboneBufs b;
-  OPP_TRY(backbone_prepare(ctx, H, W, a, b));
+  plan_backbone(ctx, 1, H, W, true, a, b);
+  OPP_CHECK_WS(a.ok, "backbone: workspace too small");
   OPP_TRY(backbone_trunk(ctx, image, H, W, feat_c, b, (hipStream_t)stream));
   return backbone_fine(ctx, H, W, feat_c, feat_f, b, FineWant::Whole, (hipStream_t)stream);
 }
@@ -1453,24 +1443,22 @@ extern "C" int opp_backbone(opp_ctx* ctx, const float* image, int H, int W, floa
 // ----------------------------------------------------------------------------------------
 namespace {
 
-// whether the statistics of encode_points_impl fit behind a's current offset (a dry run: a itself is left alone)
-bool encode_points_fits(const opp_ctx* c, const Arena& a) {
-  if (!c->cfg.kpt_enc_enable) return true;
-  Arena probe = a;
-  probe.f(8);
-  probe.f(8);
-  return probe.ok;
+// the point encoder's share of a workspace: bbox statistics of the keypoints and of the extent reference (nothing with the encoder off)
+struct PointBufs {
+  float *stats = nullptr, *stats0 = nullptr;
+};
+size_t plan_encode_points(const opp_ctx* c, Arena& a, PointBufs& b) {
+  if (c->cfg.kpt_enc_enable) {
+    b.stats = a.f(8);
+    b.stats0 = a.f(8);
+  }
+  return a.peak;
 }
 
-int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n, float* t3, Arena& a, hipStream_t s) {
+int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n, float* t3, const PointBufs& b, hipStream_t s) {
   const int C = c->cfg.coarse_d_model;
   if (c->cfg.kpt_enc_enable) {
-    float* stats = a.f(8);
-    float* stats0 = a.f(8);
-    if (!a.ok) {
-      opp_set_error("encode_points: workspace too small");
-      return OPP_ERR_WORKSPACE;
-    }
+    float *const stats = b.stats, *const stats0 = b.stats0;
     OPP_TRY(opp_kpt_stats(kpts, n, stats, s));               // utils/normalize.py:16-26
     if (c->kpt_extent_ref && c->kpt_extent_ref != kpts) {
       // B > 1: the scaling comes from the bbox extent of batch element 0, the centre from this sample (quirk q4)
@@ -1486,13 +1474,9 @@ int encode_points_impl(opp_ctx* c, const float* kpts, const float* bank_c, int n
 }
 
 int coarse_tokens_impl(opp_ctx* c, const float* feat_c, const float* pe, int L, const float* kpts, const float* bank_c,
-                       int n, const float* tokens3d_pre, float* tokens, Arena& a, hipStream_t s) {
+                       int n, const float* tokens3d_pre, float* tokens, const PointBufs& b, hipStream_t s) {
   const int C = c->cfg.coarse_d_model;
-  if (!tokens3d_pre && !encode_points_fits(c, a)) {     // refused before the image half is launched
-    opp_set_error("coarse_tokens: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  if (pe && tokens3d_pre)      // the serving case: one launch for feat_c + pe and the cached point tokens
+  if (pe && tokens3d_pre)     // the serving case: one launch for feat_c + pe and the cached point tokens
     return opp_add_cat(feat_c, pe, (size_t)L * C, tokens3d_pre, (size_t)n * C, tokens, s);
   if (pe) {
     OPP_TRY(opp_add(feat_c, pe, tokens, (size_t)L * C, s));   // OnePosePlusModel.py:137-142
@@ -1508,11 +1492,15 @@ int coarse_tokens_impl(opp_ctx* c, const float* feat_c, const float* pe, int L, 
     }
     return OPP_OK;
   }
-  return encode_points_impl(c, kpts, bank_c, n, t3, a, s);
+  return encode_points_impl(c, kpts, bank_c, n, t3, b, s);
 }
 
-struct TrBufs {
-  float *qkv, *msg, *mrg, *hid, *kv, *ks, *scratch;
+// what a linear attention needs beside its rows, and what an encoder walk adds to it
+struct AttnBufs {
+  float *kv, *ks, *scratch;
+};
+struct TrBufs : AttnBufs {
+  float *qkv, *msg, *mrg, *hid;
 };
 
 // scratch floats of the linear attention of (n_seg x (len0 + len1)) tokens: chunk partials of the KV reduction
@@ -1551,25 +1539,19 @@ int run_linattn(const float* qkv, int C, int D, int n_seg, int len0, int len1, b
   return opp_linattn_apply(q1, 3 * C, cross ? kv0 : kv1, cross ? ks0 : ks1, msg + (size_t)T0 * C, C, n_seg, len1, cross ? len0 : len1, C, D, eps, s);
 }
 
+size_t plan_linear_attention(int C, int D, int n_seg, int len0, int len1, Arena& a, AttnBufs& b) {
+  b.kv = a.f((size_t)2 * n_seg * C * D);
+  b.ks = a.f((size_t)2 * n_seg * C);
+  b.scratch = a.f(linattn_scratch_floats(C, D, n_seg, len0, len1));
+  return a.peak;
+}
 size_t plan_transformer(int C, int D, int n_seg, int len0, int len1, Arena& a, TrBufs& b) {
   const size_t T = (size_t)n_seg * (len0 + len1);
   b.qkv = a.f(T * 3 * C);
   b.msg = a.f(T * C);
   b.mrg = a.f(T * C);
   b.hid = a.f(T * 2 * C);
-  b.kv = a.f((size_t)2 * n_seg * C * D);
-  b.ks = a.f((size_t)2 * n_seg * C);
-  b.scratch = a.f(linattn_scratch_floats(C, D, n_seg, len0, len1));
-  return a.off;
-}
-
-// whether plan_transformer fits behind a's current offset (a dry run: a itself is left alone) -- for the entries that launch other
-// work in front of their transformer and must refuse a short workspace before that
-bool transformer_fits(int C, int D, int n_seg, int len0, int len1, const Arena& a) {
-  Arena probe = a;
-  TrBufs b;
-  plan_transformer(C, D, n_seg, len0, len1, probe, b);
-  return probe.ok;
+  return plan_linear_attention(C, D, n_seg, len0, len1, a, b);
 }
 
 struct LnArgs {   // LayerNorm fused into the GEMM epilogue (output rows = whole tile rows)
@@ -1761,26 +1743,28 @@ OppEncChain enc_chain_of(const EncLayerDesc& e, float* X, int C, const float* ms
 // reduces stream 0 only (the 3D stream's share comes from `pre`).  OPP_PREFIX_MAKE (len0 = 0): layer 0 on the 3D stream, then the
 // layer-1 projection and KV / Ksum of that stream into `pre`, and stop.  Rows are independent in every kernel of a layer and the
 // chunking of the KV reduction is per stream, so both modes reproduce the bits of the full evaluation.
-int transformer_impl(const EncLevel& lv, float* X, int n_seg, int len0, int len1, Arena& a, hipStream_t s, int h2, const TrOpts& o) {
-  const std::vector<EncLayerDesc>& layers = lv.layers;
-  const int C = lv.C, D = lv.D();
-  const int T = n_seg * (len0 + len1);
-  const ObjPrefix* pre = o.pre;
-  if (T == 0 || layers.empty()) return OPP_OK;
+// no tokens or no layers: transformer_impl returns at once, and a call that runs nothing else needs no workspace
+bool transformer_is_noop(const EncLevel& lv, int n_seg, int len0, int len1) { return n_seg * (len0 + len1) == 0 || lv.layers.empty(); }
+// the argument checks of transformer_impl: an entry asks them before it plans, so that an argument error wins over a short workspace
+int transformer_checks(const EncLevel& lv, int n_seg, int len0, int len1, int h2, const TrOpts& o) {
+  if (transformer_is_noop(lv, n_seg, len0, len1)) return OPP_OK;
   if (lv.full) {
     OPP_CHECK_ARG(h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3, "transformer: full attention runs in fp32 or bf16x3");
     OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: full attention needs both token streams");
   }
   if (o.prefix_mode != OPP_PREFIX_NONE)
-    OPP_CHECK_ARG(pre && !lv.full && n_seg == 1 && C == 256 && D == 32 && o.fusion == 2 && h2 == OPP_PREC_BF16X3 && layers.size() >= 2 &&
+    OPP_CHECK_ARG(o.pre && !lv.full && n_seg == 1 && lv.C == 256 && lv.D() == 32 && o.fusion == 2 && h2 == OPP_PREC_BF16X3 && lv.layers.size() >= 2 &&
                       !lv.is_cross[0] && lv.is_cross[1] && (o.prefix_mode == OPP_PREFIX_USE || len0 == 0),
                   "transformer: object prefix on an unsupported configuration");
-  TrBufs b;
-  plan_transformer(C, D, n_seg, len0, len1, a, b);
-  if (!a.ok) {
-    opp_set_error("transformer: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+  return OPP_OK;
+}
+int transformer_impl(const EncLevel& lv, float* X, int n_seg, int len0, int len1, const TrBufs& b, hipStream_t s, int h2, const TrOpts& o) {
+  const std::vector<EncLayerDesc>& layers = lv.layers;
+  const int C = lv.C, D = lv.D();
+  const int T = n_seg * (len0 + len1);
+  const ObjPrefix* pre = o.pre;
+  if (transformer_is_noop(lv, n_seg, len0, len1)) return OPP_OK;
+  OPP_TRY(transformer_checks(lv, n_seg, len0, len1, h2, o));
   const float eps_attn = 1e-6f, eps_ln = 1e-5f;
   // the path, as far as shape and configuration decide it (what depends on a layer's packed pointers is asked per layer)
   const EncSwitches sw = enc_switches();
@@ -1865,7 +1849,10 @@ extern "C" int opp_coarse_tokens(opp_ctx* ctx, const float* feat_c, const float*
   OPP_CHECK_ARG(ctx->tr_packed, "coarse_tokens: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(L > 0 && n > 0, "coarse_tokens: empty input");
   Arena a(ws, ws_bytes);
-  return coarse_tokens_impl(ctx, feat_c, pe, L, kpts, bank_c, n, nullptr, tokens, a, (hipStream_t)stream);
+  PointBufs b;
+  plan_encode_points(ctx, a, b);
+  OPP_CHECK_WS(a.ok, "coarse_tokens: workspace too small");
+  return coarse_tokens_impl(ctx, feat_c, pe, L, kpts, bank_c, n, nullptr, tokens, b, (hipStream_t)stream);
 }
 
 extern "C" int opp_encode_points(opp_ctx* ctx, const float* kpts, const float* bank_c, int n, float* tokens3d, void* ws,
@@ -1873,7 +1860,10 @@ extern "C" int opp_encode_points(opp_ctx* ctx, const float* kpts, const float* b
   OPP_CHECK_ARG(ctx && ctx->packed && kpts && bank_c && tokens3d && ws && n > 0, "encode_points: bad argument");
   OPP_CHECK_ARG(ctx->tr_packed, "encode_points: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   Arena a(ws, ws_bytes);
-  return encode_points_impl(ctx, kpts, bank_c, n, tokens3d, a, (hipStream_t)stream);
+  PointBufs b;
+  plan_encode_points(ctx, a, b);
+  OPP_CHECK_WS(a.ok, "encode_points: workspace too small");
+  return encode_points_impl(ctx, kpts, bank_c, n, tokens3d, b, (hipStream_t)stream);
 }
 
 // ---- per-object prefix of the coarse transformer (see ObjPrefix above) ---------------------------------------------------
@@ -1906,27 +1896,21 @@ extern "C" int opp_object_prefix(opp_ctx* ctx, const float* tokens3d, int n_poin
                 "object_prefix: prefix buffer too small or not 16-byte aligned");
   hipStream_t s = (hipStream_t)stream;
   ObjPrefix pre = obj_prefix_view(static_cast<float*>(prefix), C, D, n_points);
+  const TrOpts opts = {.fusion = ctx->cfg.encoder_fusion, .prefix_mode = OPP_PREFIX_MAKE, .pre = &pre};
+  OPP_TRY(transformer_checks(lv, 1, 0, n_points, gemm_prec(ctx->cfg), opts));
   Arena a(ws, ws_bytes);
-  OPP_CHECK_WS(transformer_fits(C, D, 1, 0, n_points, a), "object_prefix: workspace too small");
+  TrBufs b;
+  plan_transformer(C, D, 1, 0, n_points, a, b);
+  OPP_CHECK_WS(a.ok, "object_prefix: workspace too small");
   OPP_TRY(copy_f(pre.x1, tokens3d, (size_t)n_points * C, s));
-  return transformer_impl(lv, pre.x1, 1, 0, n_points, a, s, gemm_prec(ctx->cfg),
-                          {.fusion = ctx->cfg.encoder_fusion, .prefix_mode = OPP_PREFIX_MAKE, .pre = &pre});
+  return transformer_impl(lv, pre.x1, 1, 0, n_points, b, s, gemm_prec(ctx->cfg), opts);
 }
-
-namespace {
-size_t plan_linear_attention(int C, int D, int n_seg, int len0, int len1, Arena& a, float** kv, float** ks, float** scratch) {
-  *kv = a.f((size_t)2 * n_seg * C * D);
-  *ks = a.f((size_t)2 * n_seg * C);
-  *scratch = a.f(linattn_scratch_floats(C, D, n_seg, len0, len1));
-  return a.off;
-}
-}  // namespace
 
 extern "C" size_t opp_linear_attention_workspace_bytes(int n_seg, int len0, int len1, int C, int nhead) {
   if (n_seg <= 0 || nhead <= 0 || C % nhead) return 0;
   Arena a(nullptr, 0);
-  float *kv, *ks, *sc;
-  return opp_align(plan_linear_attention(C, C / nhead, n_seg, len0, len1, a, &kv, &ks, &sc)) + 256;
+  AttnBufs b;
+  return opp_align(plan_linear_attention(C, C / nhead, n_seg, len0, len1, a, b)) + 256;
 }
 
 extern "C" int opp_linear_attention(const float* qkv, int n_seg, int len0, int len1, int C, int nhead, int cross, float* msg,
@@ -1934,13 +1918,10 @@ extern "C" int opp_linear_attention(const float* qkv, int n_seg, int len0, int l
   OPP_CHECK_ARG(qkv && msg && ws, "linear_attention: null argument");
   OPP_CHECK_ARG(n_seg > 0 && len0 > 0 && len1 > 0 && nhead > 0 && C % nhead == 0, "linear_attention: bad shape");
   Arena a(ws, ws_bytes);
-  float *kv, *ks, *sc;
-  plan_linear_attention(C, C / nhead, n_seg, len0, len1, a, &kv, &ks, &sc);
-  if (!a.ok) {
-    opp_set_error("linear_attention: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  return run_linattn(qkv, C, C / nhead, n_seg, len0, len1, cross != 0, kv, ks, sc, msg, 1e-6f, (hipStream_t)stream);
+  AttnBufs b;
+  plan_linear_attention(C, C / nhead, n_seg, len0, len1, a, b);
+  OPP_CHECK_WS(a.ok, "linear_attention: workspace too small");
+  return run_linattn(qkv, C, C / nhead, n_seg, len0, len1, cross != 0, b.kv, b.ks, b.scratch, msg, 1e-6f, (hipStream_t)stream);
 }
 
 extern "C" size_t opp_full_attention_workspace_bytes(int n_seg, int len0, int len1, int C, int nhead) {
@@ -1985,13 +1966,18 @@ extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg
   OPP_CHECK_ARG(ctx && ctx->packed && tokens && ws, "transformer: null argument");
   OPP_CHECK_ARG(ctx->tr_packed, "transformer: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(which == 0 || which == 1, "transformer: which must be 0 or 1");
-  Arena a(ws, ws_bytes);
   const EncLevel lv = level_of(ctx, which);
   if (which == 0 && lv.full)
     OPP_CHECK_ARG(n_seg != 1 || !ctx->query_mask, "transformer: full attention with a query mask is unsupported (upstream FullAttention indexes the "
                                                   "None q_mask of the cross layers, linear_attention.py:84-85)");
-  return transformer_impl(lv, tokens, n_seg, len0, len1, a, (hipStream_t)stream, gemm_prec(ctx->cfg),
-                          {.mask0 = which == 0 && n_seg == 1 ? ctx->query_mask : nullptr, .fusion = ctx->cfg.encoder_fusion});
+  if (transformer_is_noop(lv, n_seg, len0, len1)) return OPP_OK;
+  const TrOpts opts = {.mask0 = which == 0 && n_seg == 1 ? ctx->query_mask : nullptr, .fusion = ctx->cfg.encoder_fusion};
+  OPP_TRY(transformer_checks(lv, n_seg, len0, len1, gemm_prec(ctx->cfg), opts));
+  Arena a(ws, ws_bytes);
+  TrBufs b;
+  plan_transformer(lv.C, lv.D(), n_seg, len0, len1, a, b);
+  OPP_CHECK_WS(a.ok, "transformer: workspace too small");
+  return transformer_impl(lv, tokens, n_seg, len0, len1, b, (hipStream_t)stream, gemm_prec(ctx->cfg), opts);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2015,21 +2001,15 @@ size_t plan_coarse_match(const opp_ctx* c, int n, int L, Arena& a, MatchBufs& b)
   b.two_sweep = b.sprec == OPP_PREC_BF16X3 && c->cfg.score_two_sweep && C % 32 == 0 && (size_t)n * L < (1ull << 31) &&
                 (size_t)(n > L ? n : L) * C * 6 < (1ull << 31);
   b.f3_split = b.two_sweep ? a.f(split_floats((size_t)n * C, b.sprec)) : nullptr;
-  return a.off;
+  return a.peak;
 }
 
 int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int hc, int wc, const float* kpts, float base_scale,
                       const float* qscale, float* conf, long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c,
-                      float* mkpts_3d, int* count, Arena& a, hipStream_t s) {
+                      float* mkpts_3d, int* count, const MatchBufs& mb, hipStream_t s) {
   const int C = c->cfg.coarse_d_model, L = hc * wc;
   // coarse_matching.feat_norm_method: "sqrt_feat_dim" divides both token sets by sqrt(C), "none" leaves them (coarse_matching.py:46-50)
   const float feat_mul = c->cfg.feat_norm == 1 ? 1.0f : 1.0f / (float)C;
-  MatchBufs mb;
-  plan_coarse_match(c, n, L, a, mb);
-  if (!a.ok) {
-    opp_set_error("coarse_match: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
   float *const scratch = mb.scratch, *const stats = mb.stats, *const f2_split = mb.f2_split, *const f3_split = mb.f3_split;
   const int sprec = mb.sprec;
   const bool two_sweep = mb.two_sweep;
@@ -2113,7 +2093,10 @@ extern "C" int opp_coarse_match(opp_ctx* ctx, const float* f3, const float* f2, 
                 "coarse_match: null argument");
   OPP_CHECK_ARG(n > 0 && hc > 0 && wc > 0, "coarse_match: empty input");
   Arena a(ws, ws_bytes);
-  return coarse_match_impl(ctx, f3, f2, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, a,
+  MatchBufs b;
+  plan_coarse_match(ctx, n, hc * wc, a, b);
+  OPP_CHECK_WS(a.ok, "coarse_match: workspace too small");
+  return coarse_match_impl(ctx, f3, f2, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, b,
                            (hipStream_t)stream);
 }
 
@@ -2122,12 +2105,31 @@ extern "C" int opp_coarse_match(opp_ctx* ctx, const float* f3, const float* f2, 
 // ----------------------------------------------------------------------------------------
 namespace {
 
-size_t plan_forward_coarse(const opp_ctx* c, int H, int W, int n, Arena& a, float** feat_c, float** tokens) {
-  const int C = c->cfg.coarse_d_model;
-  const size_t L = (size_t)(H / 8) * (W / 8);
-  *feat_c = a.f(L * C);
-  *tokens = a.f((L + n) * C);
-  return a.off;
+struct CoarseBufs {
+  float *feat_c, *tokens;
+  BackboneBufs bb;
+  PointBufs pts;
+  TrBufs tr;
+  MatchBufs match;
+};
+// feat_c and the tokens live for the whole call.  Behind them the backbone's maps, then -- one after another on the same bytes -- the
+// tokeniser's statistics, the transformer and the matcher; overlap (the fine branch runs beside the coarse level): the backbone's maps
+// stay live until the join, and the three share what lies behind them
+size_t plan_forward_coarse(const opp_ctx* c, int H, int W, int n, bool overlap, Arena& a, CoarseBufs& b) {
+  const EncLevel lv = level_of(c, 0);
+  const int L = (H / 8) * (W / 8);
+  b.feat_c = a.f((size_t)L * lv.C);
+  b.tokens = a.f(((size_t)L + n) * lv.C);
+  size_t mark = a.mark();
+  plan_backbone(c, 1, H, W, true, a, b.bb);
+  if (overlap) mark = a.mark();
+  a.rewind(mark);
+  plan_encode_points(c, a, b.pts);
+  a.rewind(mark);
+  plan_transformer(lv.C, lv.D(), 1, L, n, a, b.tr);
+  a.rewind(mark);
+  plan_coarse_match(c, n, L, a, b.match);
+  return a.peak;
 }
 
 // The FPN fine branch (six chip-filling convolutions that only the fine stage needs) beside the coarse level (many short launches that leave
@@ -2170,16 +2172,10 @@ struct SideBranch {
 extern "C" size_t opp_forward_coarse_workspace_bytes(const opp_ctx* ctx, int H, int W, int n) {
   if (!ctx) return 0;
   Arena a(nullptr, 0);
-  float *fc, *tk;
-  size_t base = opp_align(plan_forward_coarse(ctx, H, W, n, a, &fc, &tk));
-  const int L = (H / 8) * (W / 8);
-  size_t s1 = opp_backbone_workspace_bytes(ctx, H, W);
-  size_t s2 = opp_transformer_workspace_bytes(ctx, 0, 1, L, n);
-  size_t s3 = opp_coarse_match_workspace_bytes(ctx, n, L);
-  if (ctx->cfg.fpn_overlap) return base + s1 + (s2 > s3 ? s2 : s3) + 2048;   // the fine branch runs beside the coarse level
-  size_t m = s1 > s2 ? s1 : s2;
-  m = m > s3 ? m : s3;
-  return base + m + 1024;
+  CoarseBufs b;
+  // margin: 2048 (1024 on one stream) and the 256 of each stage query this number was once the sum of -- two with overlap, else one
+  const bool overlap = ctx->cfg.fpn_overlap != 0;
+  return opp_align(plan_forward_coarse(ctx, H, W, n, overlap, a, b)) + (overlap ? 2560 : 1280);
 }
 
 extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W, const float* pe, const float* kpts,
@@ -2194,59 +2190,44 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   OPP_CHECK_ARG(!ctx->cfg.pos_enc_enable || pe, "forward_coarse: positional encoding enabled but pe is null");
   OPP_CHECK_ARG(!ctx->cfg.coarse_attention || !ctx->query_mask, "forward_coarse: full attention with a query mask is unsupported (upstream "
                                                                 "FullAttention indexes the None q_mask of the cross layers, linear_attention.py:84-85)");
+  OPP_TRY(backbone_checks(ctx, H, W));
   hipStream_t s = (hipStream_t)stream;
-  Arena a(ws, ws_bytes);
-  float *feat_c, *tokens;
-  plan_forward_coarse(ctx, H, W, n, a, &feat_c, &tokens);
-  if (!a.ok) {
-    opp_set_error("forward_coarse: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  size_t mark = a.off;
   const EncLevel lv = level_of(ctx, 0);
   const int hc = H / 8, wc = W / 8, L = hc * wc, C = lv.C;
   const bool keep_inputs = !feat_f && ctx->fine_x1 && ctx->fine_x2o;   // opp_set_fine_patch_buffers: x1 / x2_out land in the caller's buffers
   const FineWant want = feat_f ? FineWant::Whole : (keep_inputs ? FineWant::Quarter : FineWant::None);
   const bool overlap = want != FineWant::None && ctx->cfg.fpn_overlap;
-  {   // the stages behind the backbone share what the workspace has left: all of their plans are tried before the first launch
-    Arena probe = a;
-    BackboneBufs bb;
-    plan_backbone(ctx, 1, H, W, true, probe, bb);
-    if (!overlap) probe.off = mark;                  // one stream: the later stages reuse the backbone's maps
-    const size_t rest = probe.off;
-    MatchBufs mb;
-    plan_coarse_match(ctx, n, L, probe, mb);
-    probe.off = rest;
-    OPP_CHECK_WS(probe.ok && transformer_fits(C, lv.D(), 1, L, n, probe) && (tokens3d_pre || encode_points_fits(ctx, probe)),
-                 "forward_coarse: workspace too small");
+  // resident object with a transformer prefix (opp_set_object_prefix): its 3D tokens enter already past layer 0
+  const bool use_prefix = ctx->obj_prefix != nullptr && ctx->obj_prefix_n == n && tokens3d_pre != nullptr && obj_prefix_ok(ctx);
+  ObjPrefix pre;
+  if (use_prefix) pre = obj_prefix_view(const_cast<float*>(ctx->obj_prefix), C, lv.D(), n);
+  // full attention: use_prefix is false (obj_prefix_ok) and the query mask was refused above
+  const TrOpts tr_opts = {.mask0 = ctx->query_mask, .fusion = ctx->cfg.encoder_fusion, .prefix_mode = use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE,
+                          .pre = use_prefix ? &pre : nullptr};
+  OPP_TRY(transformer_checks(lv, 1, L, n, gemm_prec(ctx->cfg), tr_opts));
+  Arena a(ws, ws_bytes);
+  CoarseBufs b;
+  plan_forward_coarse(ctx, H, W, n, overlap, a, b);
+  OPP_CHECK_WS(a.ok, "forward_coarse: workspace too small");
+  if (keep_inputs) {   // caller-owned buffers receive x1 / x2_out instead of the workspace (match-driven fine branch)
+    b.bb.x1 = ctx->fine_x1;
+    b.bb.x2o = ctx->fine_x2o;
   }
   SideBranch side{ctx, s};
   if (overlap) OPP_TRY(side.ensure());
   {
     AspScope asp_scope;
-    BackboneBufs b;
-    OPP_TRY(backbone_prepare(ctx, H, W, a, b, keep_inputs ? ctx->fine_x1 : nullptr, keep_inputs ? ctx->fine_x2o : nullptr));
-    OPP_TRY(backbone_trunk(ctx, image, H, W, feat_c, b, s));
-    if (overlap) mark = a.off;                       // the backbone buffers stay alive until the join
+    OPP_TRY(backbone_trunk(ctx, image, H, W, b.feat_c, b.bb, s));
     const bool forked = overlap && side.fork();
-    const int rc = backbone_fine(ctx, H, W, feat_c, feat_f, b, want, forked ? ctx->side_stream : s);
+    const int rc = backbone_fine(ctx, H, W, b.feat_c, feat_f, b.bb, want, forked ? ctx->side_stream : s);
     if (forked) side.join();
     OPP_TRY(rc);
   }
-  a.off = mark;
-  // resident object with a transformer prefix (opp_set_object_prefix): its 3D tokens enter already past layer 0
-  const bool use_prefix = ctx->obj_prefix != nullptr && ctx->obj_prefix_n == n && tokens3d_pre != nullptr && obj_prefix_ok(ctx);
-  ObjPrefix pre;
-  if (use_prefix) pre = obj_prefix_view(const_cast<float*>(ctx->obj_prefix), C, lv.D(), n);
-  OPP_TRY(coarse_tokens_impl(ctx, feat_c, ctx->cfg.pos_enc_enable ? pe : nullptr, L, kpts, bank_c, n, use_prefix ? pre.x1 : tokens3d_pre, tokens, a, s));
-  a.off = mark;
-  // full attention: use_prefix is false (obj_prefix_ok) and the query mask was refused on entry
-  OPP_TRY(transformer_impl(lv, tokens, 1, L, n, a, s, gemm_prec(ctx->cfg),
-                           {.mask0 = ctx->query_mask, .fusion = ctx->cfg.encoder_fusion, .prefix_mode = use_prefix ? OPP_PREFIX_USE : OPP_PREFIX_NONE,
-                            .pre = use_prefix ? &pre : nullptr}));
-  a.off = mark;
-  return coarse_match_impl(ctx, tokens + (size_t)L * C, tokens, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c,
-                           mkpts_3d, count, a, s);
+  OPP_TRY(coarse_tokens_impl(ctx, b.feat_c, ctx->cfg.pos_enc_enable ? pe : nullptr, L, kpts, bank_c, n, use_prefix ? pre.x1 : tokens3d_pre, b.tokens,
+                             b.pts, s));
+  OPP_TRY(transformer_impl(lv, b.tokens, 1, L, n, b.tr, s, gemm_prec(ctx->cfg), tr_opts));
+  return coarse_match_impl(ctx, b.tokens + (size_t)L * C, b.tokens, n, hc, wc, kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c,
+                           mkpts_3d, count, b.match, s);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2255,25 +2236,40 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
 namespace {
 // loftr_fine + FineMatching on the window tokens X [M * WW][C] and point tokens f3 = X + M * WW * C (OnePosePlusModel.py:187-201)
 int fine_tail(opp_ctx* ctx, float* X, int M, const float* mkpts_c, float base_scale, const float* qscale, int run_transformer, float* expec_f,
-              float* mkpts_f, Arena& a, hipStream_t s) {
+              float* mkpts_f, const TrBufs& tr, hipStream_t s) {
   const int C = ctx->cfg.fine_d_model, Wwin = ctx->cfg.fine_window, WW = Wwin * Wwin;
   float* f3 = X + (size_t)M * WW * C;
-  if (run_transformer) OPP_TRY(transformer_impl(level_of(ctx, 1), X, M, WW, 1, a, s, gemm_prec(ctx->cfg), {.fusion = ctx->cfg.encoder_fusion}));
+  if (run_transformer) OPP_TRY(transformer_impl(level_of(ctx, 1), X, M, WW, 1, tr, s, gemm_prec(ctx->cfg), {.fusion = ctx->cfg.encoder_fusion}));
   const float temp = (float)(1.0 / sqrt((double)C));   // fine_matching.py:82
   return opp_fine_head(f3, C, X, C, M, Wwin, C, temp, mkpts_c, base_scale, qscale, expec_f, mkpts_f, s);
 }
+// fine_tail's transformer behind what the entry has planned so far.  The size queries of the fine entries have no run_transformer argument,
+// so the share of loftr_fine is planned whether this call runs it or not: what the query reports is what a call needs
+size_t plan_fine_tail(const opp_ctx* c, int M, Arena& a, TrBufs& tr) {
+  const EncLevel lv = level_of(c, 1);
+  return plan_transformer(lv.C, lv.D(), M, c->cfg.fine_window * c->cfg.fine_window, 1, a, tr);
+}
+// the argument checks of fine_tail's transformer (asked before the plan, as in every entry that runs one)
+int fine_tail_checks(const opp_ctx* c, int M, int run_transformer) {
+  if (!run_transformer) return OPP_OK;
+  return transformer_checks(level_of(c, 1), M, c->cfg.fine_window * c->cfg.fine_window, 1, gemm_prec(c->cfg), {.fusion = c->cfg.encoder_fusion});
+}
 
-// whether fine_tail's transformer fits behind a's current offset: asked before the first launch of a fine entry.  The size queries of the
-// fine entries have no run_transformer argument, so the share of loftr_fine is asked for whether this call runs it or not: what the
-// query reports is what a call needs
-bool fine_tail_fits(const opp_ctx* ctx, int M, const Arena& a) {
-  const EncLevel lv = level_of(ctx, 1);
-  return transformer_fits(lv.C, lv.D(), M, ctx->cfg.fine_window * ctx->cfg.fine_window, 1, a);
+// opp_fine: [M * WW window tokens ; M point tokens], then the transformer
+struct FineBufs {
+  float* X;
+  TrBufs tr;
+};
+size_t plan_fine(const opp_ctx* c, int M, Arena& a, FineBufs& b) {
+  const int WW = c->cfg.fine_window * c->cfg.fine_window;
+  b.X = a.f((size_t)M * (WW + 1) * c->cfg.fine_d_model);
+  return plan_fine_tail(c, M, a, b.tr);
 }
 
 struct PatchBufs {
   float *X, *xa, *l1, *u1, *sk;
   size_t sk_floats;
+  TrBufs tr;
 };
 size_t plan_fine_patches(const opp_ctx* c, int M, Arena& a, PatchBufs& b) {
   const int C = c->cfg.fine_d_model, W = c->cfg.fine_window, WW = W * W, P9 = W + 4, P7 = W + 2;
@@ -2286,7 +2282,7 @@ size_t plan_fine_patches(const opp_ctx* c, int M, Arena& a, PatchBufs& b) {
   const size_t r1 = (size_t)M * P7 * P7 * c2, r2 = (size_t)M * WW * C;
   b.sk_floats = 4 * (r1 > r2 ? r1 : r2);
   b.sk = a.f(b.sk_floats);
-  return a.off;
+  return plan_fine_tail(c, M, a, b.tr);
 }
 }  // namespace
 
@@ -2306,8 +2302,7 @@ extern "C" size_t opp_fine_patches_workspace_bytes(const opp_ctx* ctx, int M) {
   if (!ctx || M <= 0) return 256;
   Arena a(nullptr, 0);
   PatchBufs b;
-  const int WW = ctx->cfg.fine_window * ctx->cfg.fine_window;
-  return opp_align(plan_fine_patches(ctx, M, a, b)) + opp_transformer_workspace_bytes(ctx, 1, M, WW, 1) + 2048;
+  return opp_align(plan_fine_patches(ctx, M, a, b)) + 2304;   // margin: 2048 and the 256 of the transformer query it was once summed with
 }
 
 // Fine level straight from x1 / x2_out of opp_forward_coarse (opp_set_fine_patch_buffers): the three convolutions behind them
@@ -2329,14 +2324,11 @@ extern "C" int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_o
   const int c1 = pad32(ctx->cfg.block_dims[0]), c2 = pad32(ctx->cfg.block_dims[1]);
   OPP_CHECK_ARG(ctx->l1_out2b.cout_pad() == C, "fine_patches: fine map width %d != fine d_model %d", ctx->l1_out2b.cout_pad(), C);
   OPP_CHECK_ARG((size_t)M * P9 * P9 * c2 * 4 < (1ull << 31), "fine_patches: too many matches for 32-bit buffer addressing (%d)", M);
+  OPP_TRY(fine_tail_checks(ctx, M, run_transformer));
   Arena a(ws, ws_bytes);
   PatchBufs b;
   plan_fine_patches(ctx, M, a, b);
-  if (!a.ok) {
-    opp_set_error("fine_patches: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  OPP_CHECK_WS(fine_tail_fits(ctx, M, a), "fine_patches: workspace too small");
+  OPP_CHECK_WS(a.ok, "fine_patches: workspace too small");
   OppProfScope prof(OPP_PROF_FINE, s, (double)M * ((double)(WW + 1) * C * 4.0 + 5 * 4.0));
   const int hp = gemm_prec(ctx->cfg);
   const int org = -(Wwin / 2);                      // window origin relative to the match's fine-map pixel (fine_preprocess.py:41-47: padding W // 2)
@@ -2356,7 +2348,7 @@ extern "C" int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_o
   OPP_TRY(run_conv(b.u1, P7, P7, ctx->l1_out2b, 1, nullptr, OPP_RES_NONE, OPP_ACT_NONE, b.X, s, hp, {.Bn = M, .pad = 0, .splitk_force = split_b}));
   OPP_TRY(opp_patch_zero_oob(b.X, C, j_ids, M, wc, stride, org, Wwin, Hf, Wf, s));
   OPP_TRY(opp_fine_points_gather(bank_f, n, i_ids, M, C, b.X + (size_t)M * WW * C, C, s));
-  return fine_tail(ctx, b.X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, a, s);
+  return fine_tail(ctx, b.X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, b.tr, s);
 }
 
 extern "C" size_t opp_backbone_fine_branch_workspace_bytes(const opp_ctx* ctx, int H, int W) {
@@ -2372,24 +2364,22 @@ extern "C" int opp_backbone_fine_branch(opp_ctx* ctx, const float* x1, const flo
   FlagScope flag_scope(ctx);
   OPP_CHECK_ARG(ctx && ctx->packed && x1 && x2_out && feat_f && ws, "backbone_fine_branch: null argument");
   OPP_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0, "backbone_fine_branch: H,W must be multiples of 8 (got %dx%d)", H, W);
+  OPP_TRY(backbone_checks(ctx, H, W));
   Arena a(ws, ws_bytes);
   BackboneBufs b{};
   plan_fine_branch(ctx, H, W, a, b);
-  if (!a.ok) {
-    opp_set_error("backbone_fine_branch: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
+  OPP_CHECK_WS(a.ok, "backbone_fine_branch: workspace too small");
   b.x1 = const_cast<float*>(x1);
   b.x2o = const_cast<float*>(x2_out);
   AspScope asp_scope;
-  OPP_TRY(backbone_checks(ctx, H, W));
   return backbone_fine_half(ctx, H, W, feat_f, b, (hipStream_t)stream);
 }
 
 extern "C" size_t opp_fine_workspace_bytes(const opp_ctx* ctx, int M) {
   if (!ctx || M <= 0) return 256;
-  const int C = ctx->cfg.fine_d_model, WW = ctx->cfg.fine_window * ctx->cfg.fine_window;
-  return opp_align((size_t)M * (WW + 1) * C * sizeof(float)) + opp_transformer_workspace_bytes(ctx, 1, M, WW, 1) + 1024;
+  Arena a(nullptr, 0);
+  FineBufs b;
+  return opp_align(plan_fine(ctx, M, a, b)) + 1280;   // margin: 1024 and the 256 of the transformer query it was once summed with
 }
 
 extern "C" int opp_fine(opp_ctx* ctx, const float* feat_f, int Hf, int Wf, const float* bank_f, int n, const long long* i_ids,
@@ -2403,18 +2393,16 @@ extern "C" int opp_fine(opp_ctx* ctx, const float* feat_f, int Hf, int Wf, const
   OPP_CHECK_ARG(hc > 0 && Hf % hc == 0, "fine: fine map height %d not a multiple of coarse %d", Hf, hc);
   hipStream_t s = (hipStream_t)stream;
   const int C = ctx->cfg.fine_d_model, Wwin = ctx->cfg.fine_window, WW = Wwin * Wwin;
+  OPP_TRY(fine_tail_checks(ctx, M, run_transformer));
   Arena a(ws, ws_bytes);
-  float* X = a.f((size_t)M * (WW + 1) * C);  // [M*WW window tokens ; M point tokens]
-  if (!a.ok) {
-    opp_set_error("fine: workspace too small");
-    return OPP_ERR_WORKSPACE;
-  }
-  OPP_CHECK_WS(fine_tail_fits(ctx, M, a), "fine: workspace too small");
-  float* f3 = X + (size_t)M * WW * C;
+  FineBufs b;
+  plan_fine(ctx, M, a, b);
+  OPP_CHECK_WS(a.ok, "fine: workspace too small");
+  float *const X = b.X, *const f3 = X + (size_t)M * WW * C;
   // whole fine stage as one profiled span; algorithmic bytes: windows + point descriptors gathered, outputs written
   OppProfScope prof(OPP_PROF_FINE, s, (double)M * ((double)(WW + 1) * C * 4.0 + 5 * 4.0));
   OPP_TRY(opp_fine_gather(feat_f, Hf, Wf, C, bank_f, n, i_ids, j_ids, M, wc, Hf / hc, Wwin, C, X, C, f3, C, s));
-  return fine_tail(ctx, X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, a, s);
+  return fine_tail(ctx, X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, b.tr, s);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -2633,8 +2621,7 @@ extern "C" size_t opp_conv2d_backward_workspace_bytes(int B, int Hin, int Win, i
   conv_bwd_need(n, B, Hin, Win, cin, cout, ks, stride, true, true, prec);
   Arena a(nullptr, 0);
   ConvBwdWs w;
-  conv_bwd_alloc(a, n, w);
-  return opp_align(a.off) + 256;
+  return opp_align(plan_conv_bwd(n, a, w)) + 256;
 }
 
 extern "C" int opp_conv2d_backward_nhwc(const float* x, int B, int Hin, int Win, int cin, const float* w, int cout, int ks, int stride,
@@ -2646,7 +2633,7 @@ extern "C" int opp_conv2d_backward_nhwc(const float* x, int B, int Hin, int Win,
   conv_bwd_need(n, B, Hin, Win, cin, cout, ks, stride, grad_x != nullptr, grad_w != nullptr, prec);
   Arena a(ws, ws_bytes);
   ConvBwdWs cw;
-  conv_bwd_alloc(a, n, cw);
+  plan_conv_bwd(n, a, cw);
   OPP_CHECK_WS(a.ok, "conv2d_backward: workspace too small");
   return conv_backward(x, B, Hin, Win, cin, w, cout, ks, stride, grad_y, grad_x, grad_x_add, grad_w, prec, cw, (hipStream_t)stream);
 }

@@ -356,3 +356,106 @@ def test_backbone_workspace_sizes_are_pinned_with_presplit_twins():
     for hw, (backbone, coarse) in BACKBONE_WS_ASP.items():
         assert (got[hw][0], tuple(tuple(c) for c in got[hw][1])) == (backbone, coarse), hw
         assert (got[hw][2], tuple(got[hw][3])) == BACKBONE_WS[hw][2:], hw
+
+
+# Every other size query of csrc/api.hip, at the shapes of tests/test_memory_contract_gpu.py (IMAGES, POINTS, TOKENS, MATCHER, M = 1 / 33 /
+# 300 matches, B = 1 / 3) and at the flagship shape (512 x 512, n = 5000, M = 500), recorded from the build of commit 6d0f003 (the size
+# of a call stated by a formula or a sum of nested queries beside the plans that carve it)
+WS_IMAGES = [(40, 72), (64, 96), (128, 192), (512, 512)]
+WS_POINTS = [77, 129, 257, 333, 5000]
+WS_MATCHES = [1, 33, 300, 500]
+WS_TOKENS = [(31, 1), (45, 77), (65, 129), (96, 200), (4096, 5000)]
+WS_FINE_TOKENS = [(3, 25, 1), (3, 49, 1), (3, 64, 3), (500, 25, 1)]                     # (n_seg, len0, len1) at C = 128
+WS_MATCHER = [(8, 12, 77), (16, 24, 300), (16, 32, 333), (64, 64, 5000)]              # (hc, wc, N)
+WS_BATCH = (1, 3)
+# (cin, cout, ks, stride, (H, W)): the cases of the conv2d_backward stage of the contract file
+WS_CONV_BWD = [(196, 196, 3, 1, (5, 9)), (128, 196, 3, 2, (10, 18)), (196, 256, 1, 2, (10, 18)), (64, 64, 3, 1, (24, 32)), (256, 196, 1, 1, (3, 11)),
+               (128, 196, 1, 1, (15, 20))]
+WS_SCORE_CTX = {"bf16x3-dense": ("bf16x3", 0), "bf16x3-two_sweep": ("bf16x3", 1), "bf16x3-single": ("bf16x3", 2), "fp32": ("fp32", 2)}
+
+
+_entry_ws_cache = {}
+
+
+def _entry_ws_sizes():
+    """{query name: [sizes in the order of the WS_* lists]} from the library (asked once per process)"""
+    if not _entry_ws_cache:
+        _entry_ws_cache.update(_ask_entry_ws_sizes())
+    return _entry_ws_cache
+
+
+def _ask_entry_ws_sizes():
+    import ctypes
+    from onepose_plus_plus_amd import _lib
+    lib = _lib.load()
+    ctxs = {}
+
+    def ctx_of(precision="bf16x3", score=2, window=5):
+        key = (precision, score, window)
+        if key not in ctxs:
+            cfg = default_config()
+            cfg["loftr_fine"]["window_size"] = window
+            ccfg = OnePosePlus_model(cfg).set_gemm_precision(precision).set_score_two_sweep(score)._c_config()
+            ctxs[key] = ctypes.c_void_p()
+            _lib.check(lib.opp_create(ctypes.byref(ccfg), ctypes.byref(ctxs[key])), "opp_create")
+        return ctxs[key]
+
+    try:
+        out = {}
+        for window in (5, 7):
+            out["fine-w%d" % window] = [lib.opp_fine_workspace_bytes(ctx_of(window=window), M) for M in WS_MATCHES]
+            out["fine_patches-w%d" % window] = [lib.opp_fine_patches_workspace_bytes(ctx_of(window=window), M) for M in WS_MATCHES]
+        for name, (precision, score) in WS_SCORE_CTX.items():
+            out["coarse_match-" + name] = [lib.opp_coarse_match_workspace_bytes(ctx_of(precision, score), n, hc * wc) for hc, wc, n in WS_MATCHER]
+            out["forward_coarse-" + name] = [lib.opp_forward_coarse_workspace_bytes(ctx_of(precision, score), *hw, n)
+                                             for hw, n in zip(WS_IMAGES, (77, 129, 333, 5000))]
+        out["coarse_match-null"] = [lib.opp_coarse_match_workspace_bytes(None, n, hc * wc) for hc, wc, n in WS_MATCHER]
+        out["linear_attention"] = ([lib.opp_linear_attention_workspace_bytes(1, l0, l1, 256, 8) for l0, l1 in WS_TOKENS] +
+                                   [lib.opp_linear_attention_workspace_bytes(n_seg, l0, l1, 128, 8) for n_seg, l0, l1 in WS_FINE_TOKENS])
+        out["object_prefix"] = [lib.opp_object_prefix_workspace_bytes(ctx_of(), n) for n in WS_POINTS]
+        for precision in ("bf16x3", "fp32"):
+            c = ctx_of(precision)
+            for q in ("backbone_train", "backbone_train_tape", "backbone_backward"):
+                fn = getattr(lib, "opp_%s_workspace_bytes" % q)
+                out["%s-%s" % (q, precision)] = [fn(c, B, *hw) for B in WS_BATCH for hw in WS_IMAGES]
+        for prec_name, prec in (("bf16x3", 2), ("fp32", 0)):
+            out["conv2d_backward-" + prec_name] = [lib.opp_conv2d_backward_workspace_bytes(B, *hw, cin, cout, ks, stride, prec)
+                                                   for cin, cout, ks, stride, hw in WS_CONV_BWD for B in WS_BATCH]
+        return out
+    finally:
+        for ctx in ctxs.values():
+            lib.opp_destroy(ctx)
+
+
+ENTRY_WS = {
+    "fine-w5": [133888, 4377344, 39783680, 66305280],
+    "fine_patches-w5": [468736, 15386368, 139855104, 233090304],
+    "fine-w7": [232192, 7621376, 69274880, 115457280],
+    "fine_patches-w7": [766720, 25219840, 229250304, 382082304],
+    "coarse_match-bf16x3-dense": [154880, 652032, 873472, 14816768],
+    "forward_coarse-bf16x3-dense": [39079936, 44926464, 77062656, 509332992],
+    "coarse_match-bf16x3-two_sweep": [273152, 1112832, 1384960, 22496768],
+    "forward_coarse-bf16x3-two_sweep": [39079936, 44926464, 77062656, 509332992],
+    "coarse_match-bf16x3-single": [273152, 1112832, 1384960, 22496768],
+    "forward_coarse-bf16x3-single": [39079936, 44926464, 77062656, 509332992],
+    "coarse_match-fp32": [7424, 62208, 87040, 8525312],
+    "forward_coarse-fp32": [39079936, 44926464, 77062656, 509332992],
+    "coarse_match-null": [273920, 1113600, 1385728, 22497536],
+    "linear_attention": [135424, 169216, 236800, 270592, 4900096, 78592, 78592, 78592, 13056256],
+    "object_prefix": [687360, 1093888, 2078976, 2657536, 38577408],
+    "backbone_train-bf16x3": [4968192, 10594560, 42371328, 451938560, 14899968, 31779072, 127109376, 1355811072],
+    "backbone_train_tape-bf16x3": [383232, 813312, 3246336, 34605312, 1145088, 2435328, 9734400, 103811328],
+    "backbone_backward-bf16x3": [20910592, 33943808, 73130240, 372678912, 31978240, 47485184, 146170112, 1025941760],
+    "backbone_train-fp32": [4968192, 10594560, 42371328, 451938560, 14899968, 31779072, 127109376, 1355811072],
+    "backbone_train_tape-fp32": [383232, 813312, 3246336, 34605312, 1145088, 2435328, 9734400, 103811328],
+    "backbone_backward-fp32": [19730944, 32764160, 71950592, 371499264, 30798592, 46305536, 144990464, 1024762112],
+    "conv2d_backward-bf16x3": [7790592, 7791360, 4571904, 4895232, 1226496, 1595904, 2892032, 7622912, 1040128, 1040128, 653056, 1046272],
+    "conv2d_backward-fp32": [6987776, 6988544, 4113152, 4436480, 1111808, 1481216, 2818304, 7549184, 925440, 925440, 595712, 988928],
+}
+
+
+@pytest.mark.parametrize("query", sorted(ENTRY_WS))
+def test_entry_workspace_sizes_are_pinned(query):
+    """Python allocates every call's workspace by its size query, and the entry carves the same plan out of it: the number a query reports
+    for a shape is part of the interface and must not move, whichever way the plan behind it is written."""
+    assert _entry_ws_sizes()[query] == ENTRY_WS[query]
