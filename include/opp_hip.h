@@ -713,6 +713,44 @@ int opp_pnp_loransac_batch(const float* pts2d, const float* pts3d, const int* of
                            int* inlier_mask, int* n_inliers, int* ok, int* stop, void* workspace, size_t workspace_bytes,
                            void* stream);
 
+/* ---- 2D box by matches: affine RANSAC for a batch of views (the estimator half of the reference's first-frame detector,
+ * src/local_feature_object_detector/local_feature_2D_detector.py:74-131) ------------------------------------------------------
+ * cv2.estimateAffine2D(method = RANSAC) for n_views (1..1024) views in one enqueue, as we read OpenCV 4.x (its source is not
+ * available here: parity unpinned), then the box of each view's image corners under its map and the box of the view with the
+ * most inliers.  The batch conventions are those of opp_pnp_ransac_batch: pts0 [n_total][2] (the view's image) and pts1
+ * [n_total][2] (the query frame) hold the matches of all views concatenated in view order, `offsets` [n_views + 1] (device;
+ * opp_pnp_offsets makes it from per-match view ids) delimits them, a pair of offsets that is no segment of [0, n_total] makes an
+ * empty view, seeds [n_views] is a device array.  corners [n_views][4][2] (device, doubles): the points mapped into the box, the
+ * reference's (0,0), (W,0), (0,H), (W,H) of each view's image.  fallback_box: four ints on the HOST, the box of a view without a
+ * model (the reference's image centre +- 500).
+ * Per view, with n matches: hypothesis h draws 3 distinct matches from the hash sampler of opp_pnp_ransac (n == 3: one hypothesis
+ * on matches 0, 1, 2); a sample whose SOURCE points are collinear by OpenCV's haveCollinearPoints test scores -1 and still counts
+ * as an iteration (OpenCV draws again); the 2 x 3 map is solved in closed form in float64; a match is an inlier when the squared
+ * distance of its mapped source point to its query point is <= thr_px^2; a new best needs more than max(best, 2) inliers and
+ * OpenCV's adaptive stop runs at `confidence` (>= 1: never), the stop index and best hypothesis being those of the sequential loop
+ * over h = 0, 1, ...; the inliers returned are those of the best hypothesis; with `refine` and more than 3 of them the map is the
+ * linear least-squares fit on the inliers, solved in coordinates centred on their mean (OpenCV runs 10 Levenberg-Marquardt
+ * iterations on this linear problem: the same minimiser).  The four corners are mapped, truncated towards zero to int32, and
+ * box = min x, min y, max x, max y.
+ * Outputs on the device, every entry written: affine_out [n_views][6] (row-major 2 x 3), inlier_mask [n_total] (0/1, indexed like
+ * the matches; 0 for a match no view covers), n_inliers, ok, stop [n_views], boxes [n_views][4], best_view [1] (the ok view with
+ * the most inliers, the first on ties; -1 when there is none) and best_box [4] (its box, or the fallback box).  A failed view
+ * (fewer than 3 matches, no hypothesis above 2 inliers, a mapped corner that is not finite or does not fit int32) gets the
+ * identity map, a zeroed mask segment, n_inliers = 0, ok = 0 and the fallback box; stop = 0 with fewer than 3 matches.
+ * samples_out [n_views][iterations][3] and scores_out [n_views][iterations] may be NULL; hypotheses a view does not evaluate
+ * are recorded as -1.  View v's outputs are bit for bit those of a call on its slice alone with seeds[v].  n_total = 0 is legal
+ * (every view fails).  The workspace (opp_affine_layout, csrc/affine_batch.h) holds 60 bytes per hypothesis and view. */
+size_t opp_affine2d_batch_workspace_bytes(int iterations, int n_views, int n_total);
+int opp_affine2d_ransac_batch(const float* pts0, const float* pts1, const int* offsets, int n_views, int n_total,
+                              const unsigned* seeds, const double* corners, double thr_px, int iterations,
+                              double confidence, int refine, const int* fallback_box,
+                              double* affine_out /* [n_views][6] row-major 2x3 */, int* inlier_mask /* [n_total] */,
+                              int* n_inliers, int* ok, int* stop, int* boxes /* [n_views][4] */,
+                              int* best_view /* [1] */, int* best_box /* [4] */,
+                              int* samples_out /* [n_views][iterations][3] or NULL */,
+                              int* scores_out /* [n_views][iterations] or NULL */,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- pose-error metrics (the scoring half of compute_query_pose_errors, src/utils/metric_utils.py:207-292) --------
  * Scores n_poses poses of ONE model in a single enqueue (at most three launches, no host synchronisation, no allocation):
  * query_pose_error (:91-118), add_metric's mean distance (:55-87; ADD, or ADD-S = for every TARGET point the nearest PREDICTED

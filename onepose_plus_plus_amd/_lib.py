@@ -198,6 +198,10 @@ SIGNATURES = {
     "opp_pnp_loransac_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_int,
                                        ctypes.c_double, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "opp_affine2d_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "opp_affine2d_ransac_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_double, c_int,
+                                          ctypes.c_double, c_int, POINTER(c_int), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_pose_metrics_workspace_bytes": (c_size_t, [c_int, c_int]),
     "opp_pose_metrics": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, ctypes.c_double, c_void_p,
                                  c_void_p, c_size_t, c_void_p]),

@@ -232,6 +232,20 @@ def _batch_call(options, use_pycolmap_ransac=False, batch_loransac=True):
     return ransac_PnP_batch, dict(kw, solver=solver)
 
 
+def _batch_seeds(name, seed, B):
+    """seed: an int for every sample, or B of them -> [B] int64 in [0, 2^32)"""
+    seeds = np.broadcast_to(np.asarray(seed, dtype=np.int64) & 0xFFFFFFFF, (B,)) if np.ndim(seed) == 0 else \
+        np.asarray(seed, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
+    if seeds.shape != (B,):
+        raise ValueError("%s: seed must be an int or %d ints" % (name, B))
+    return seeds
+
+
+def _seeds_to_device(seeds, device):
+    """[B] int64 in [0, 2^32) -> the device array of unsigned the batch calls read (carried as int32 bits)"""
+    return torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+
+
 def _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, device):
     """the argument checks and host-side inputs the batch calls share -> (device, K [B,3,3] float64, seeds [B], p2, p3)"""
     if (m_bids is None) == (offsets is None):
@@ -244,10 +258,7 @@ def _batch_prepare(name, K, pts_2d, pts_3d, m_bids, offsets, batch_size, seed, d
         raise ValueError("%s: K holds %d matrices, batch_size is %d" % (name, B, int(batch_size)))
     if not 1 <= B <= 1024:
         raise ValueError("%s: 1 to 1024 samples, got %d" % (name, B))
-    seeds = np.broadcast_to(np.asarray(seed, dtype=np.int64) & 0xFFFFFFFF, (B,)) if np.ndim(seed) == 0 else \
-        np.asarray(seed, dtype=np.int64).reshape(-1) & 0xFFFFFFFF
-    if seeds.shape != (B,):
-        raise ValueError("%s: seed must be an int or %d ints" % (name, B))
+    seeds = _batch_seeds(name, seed, B)
     p2 = _dev_f32(pts_2d, device).reshape(-1, 2)
     p3 = _dev_f32(pts_3d, device).reshape(-1, 3)
     if int(p3.shape[0]) != int(p2.shape[0]):
@@ -302,7 +313,7 @@ def _batch_run(name, device, Kn, fy, seeds, p2, p3, m_bids, offsets, chunk, ws_b
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
         K4 = torch.from_numpy(np.ascontiguousarray(np.stack([Kn[:, 0, 0], fy, Kn[:, 0, 2], Kn[:, 1, 2]], axis=1))).to(device)
-        seeds_d = torch.from_numpy(seeds.astype(np.uint32).view(np.int32).copy()).to(device)
+        seeds_d = _seeds_to_device(seeds, device)
         cnt = torch.zeros(3 * B + 1, dtype=torch.int32, device=device)   # n_inliers [B], ok [B], stop [B], bad ids
         off = _batch_offsets(name, lib, m_bids, offsets, B, n, cnt.data_ptr() + 12 * B, device, stream)
         out = torch.empty((B, 3, 4), dtype=torch.float64, device=device)

@@ -13,9 +13,11 @@ box and the cropped intrinsics are 8 points and a 3 x 3 product and stay on the 
 after PnP.  Decoding the file stays with the caller.  OpenCV's source is not available here: parity of the crop with
 cv2.warpAffine is unpinned (tests/crop_reference.py restates the arithmetic in two forms).
 
-The first-frame detector of the reference (`LocalFeatureObjectDetector.detect`, LoFTR matching against the SfM database images)
-needs the LoFTR submodule, which the reference checkout does not carry: it is out of scope.  `PoseTracker` takes any callable
-`detector(frame_u8, K) -> [x0, y0, x1, y1]` instead, or an explicit `box=` per frame.
+The first-frame detector of the reference (`LocalFeatureObjectDetector.detect`) is LoFTR matching against the SfM database images
+and, behind it, an affine RANSAC per view whose best view gives the box.  The estimator is built: `detect.AffineBoxDetector` runs it
+on the device for all views at once (parity with `cv2.estimateAffine2D` unpinned: OpenCV is not installed here).  The LoFTR matcher
+is not: the reference checkout does not carry that submodule, so the detector takes the caller's 2D-2D matcher.  `PoseTracker` takes
+any callable `detector(frame_u8, K) -> [x0, y0, x1, y1]` -- an `AffineBoxDetector` is one -- or an explicit `box=` per frame.
 """
 import ctypes
 
@@ -155,8 +157,8 @@ class PoseTracker:
 
     model: `OnePosePlus_model` (any callable that fills `mkpts_query_f` [M,2] and `mkpts_3d_db` [M,3] of the data dict);
     bank: `ObjectBank`; K [3,3]: intrinsics of the full frame; bbox3d [8,3]: corners of the object's 3D box;
-    detector: optional callable `detector(frame_u8, K) -> [x0, y0, x1, y1]` (the reference's LoFTR-based first-frame detector
-    needs a submodule its checkout does not carry and is not provided here).  PnP runs with the demo's arguments (demo.py:132:
+    detector: optional callable `detector(frame_u8, K) -> [x0, y0, x1, y1]`, e.g. `detect.AffineBoxDetector(matcher, ref_images)`
+    (the reference's detector behind its LoFTR matcher; the matcher itself needs a submodule the checkout does not carry).  PnP runs with the demo's arguments (demo.py:132:
     scale 1000, reprojection error 7, the pycolmap branch = solver "auto" -> "loransac"); `pnp_kwargs` override them.
 
     >>> tracker = PoseTracker(model, bank, K, bbox3d, detector=my_detector)
