@@ -111,6 +111,15 @@ typedef struct opp_config {
   /* coarse_matching.feat_norm_method (coarse_matching.py:46-54): 0 = "sqrt_feat_dim" (scores divided by C; the default), 1 = "none" / None
    * (scores as they are). */
   int feat_norm;
+  /* Not a reference key of the 2D-3D model: the layer schedule of the 2D-2D matcher (LoFTR, onepose_plus_plus_amd/loftr.py).  0 (what
+   * every 2D-3D configuration has) = a cross layer updates both streams from each other's PRE-update tokens (quirk q6); 1 = sequential:
+   * a cross layer updates stream 0 from stream 1, then stream 1 from the UPDATED stream 0, at both levels.  Each stream's q, k, v are
+   * still projected once per layer (q of stream 0 and q | k | v of stream 1 first, k | v of stream 0 after its update).  Runs with
+   * encoder_fusion 0 and linear attention only (opp_create refuses anything else), in both arithmetics, and admits fine windows up to
+   * 9 x 9 (81 + 81 tokens per match through opp_fine2d).  Honoured by opp_transformer and opp_fine2d, the stages of the 2D-2D matcher; the
+   * 2D-3D entries opp_forward_coarse, opp_fine and opp_fine_patches refuse such a context.  With more than one segment the schedule runs
+   * d_model 128 / 8 heads and at most 81 tokens per stream only (one workgroup per segment); other shapes are refused. */
+  int cross_sequential;
 } opp_config;
 
 typedef struct opp_ctx opp_ctx;
@@ -287,6 +296,29 @@ int opp_fine_patches(opp_ctx* ctx, const float* x1, const float* x2_out, int H, 
 size_t opp_backbone_fine_branch_workspace_bytes(const opp_ctx* ctx, int H, int W);
 int opp_backbone_fine_branch(opp_ctx* ctx, const float* x1, const float* x2_out, int H, int W, float* feat_f, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* ---- 2D-2D matching (LoFTR as the reference's LoFTR_for_OnePose_Plus strings it together, src/KeypointFreeSfM/loftr_for_sfm/loftr.py:16-128;
+ * the LoFTR submodule itself is absent from the reference: these entries follow the published LoFTR, parity unpinned) -------------------
+ * opp_image_tokens: tokens [L][coarse_d_model] = feat_c + pe (pe may be NULL: a copy), the coarse tokens of one image.
+ * opp_match2d: CoarseMatching of two images.  f0 [L0][C], f1 [L1][C] (L0 = h0c * w0c, L1 = h1c * w1c): sim = <f0 / sqrt(C), f1 / sqrt(C)> /
+ * match_temperature (exactly as configured), conf [L0][L1] = softmax(sim, rows) * softmax(sim, columns) is written; a pair (i, j) is kept
+ * when conf > match_thr, conf is the maximum of its row and of its column, and neither cell lies within match_border_rm cells of ANY of the
+ * four edges of its own grid; a row with several such j keeps the first; output in ascending i with capacity L0, *count (device int) = M.
+ * mkpts0_c [M][2] = (i % w0c, i / w0c) * base_scale * scale0[[1, 0]], mkpts1_c likewise from j, w1c, scale1 (scale* = device pointers to
+ * (h_scale, w_scale), or NULL = 1).  The score GEMM runs in the context's arithmetic (image 1's tokens pre-split under bf16x3).
+ * opp_fine2d: window gather of BOTH 1/2-resolution maps (NHWC [Hf][Wf][fine_d_model], W x W cells at `stride` = Hf / hc around coarse
+ * cells i_ids[m] / j_ids[m], zeros outside the map), loftr_fine on M segments of W^2 + W^2 tokens, then the expectation head of opp_fine
+ * with the CENTRE token of window 0 in the place of the 3D point token: expec_f [M][3], mkpts1_f = mkpts1_c + expec_f[:, :2] * (W / 2) *
+ * base_scale * scale1[[1, 0]].  Wf = w*c * stride and Hf a multiple of stride are required.  M <= 0 returns at once.  Both workspace-taking entries follow the workspace contract above. */
+int opp_image_tokens(opp_ctx* ctx, const float* feat_c, const float* pe, int L, float* tokens, void* stream);
+size_t opp_match2d_workspace_bytes(const opp_ctx* ctx, int L0, int L1);
+int opp_match2d(opp_ctx* ctx, const float* f0, const float* f1, int h0c, int w0c, int h1c, int w1c, float base_scale,
+                const float* scale0, const float* scale1, float* conf, long long* i_ids, long long* j_ids, float* mconf,
+                float* mkpts0_c, float* mkpts1_c, int* count, void* workspace, size_t workspace_bytes, void* stream);
+size_t opp_fine2d_workspace_bytes(const opp_ctx* ctx, int n_matches);
+int opp_fine2d(opp_ctx* ctx, const float* feat_f0, int Hf0, int Wf0, const float* feat_f1, int Hf1, int Wf1, const long long* i_ids,
+               const long long* j_ids, int n_matches, int w0c, int w1c, int stride, const float* mkpts1_c, float base_scale,
+               const float* scale1, float* expec_f, float* mkpts1_f, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- training step: coarse focal loss (Loss.compute_coarse_loss, src/lightning_model/losses.py:18-55) -------------
  * conf [n] fp32 (the B x N x L confidence matrix, 16-byte aligned), conf_gt [n] int16 (0 / 1; other values are ignored

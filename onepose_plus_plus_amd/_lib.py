@@ -45,6 +45,7 @@ class OppConfig(Structure):
         ("fine_rezero", c_int),
         ("kpt_norm", c_int),
         ("feat_norm", c_int),
+        ("cross_sequential", c_int),
     ]
 
 
@@ -114,6 +115,13 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_fine_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "opp_image_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "opp_match2d_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "opp_match2d": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p] + [c_void_p] * 7
+                    + [c_void_p, c_size_t, c_void_p]),
+    "opp_fine2d_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "opp_fine2d": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                           c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "opp_fine_head_train_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "opp_fine_head_train_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "opp_build_assignmatrix": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_void_p, c_void_p,

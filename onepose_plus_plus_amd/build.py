@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_build")
 LIB = os.path.join(HERE, "libopp_hip.so")
 SOURCES = ["gemm_mfma.hip", "gemm_ss.hip", "enc_chain.hip", "enc_layer64.hip", "stem_direct.hip", "attention.hip", "full_attention.hip", "full_attention_train.hip", "backbone.hip", "kpt.hip",
-           "coarse_match.hip", "fine.hip", "pnp.hip", "pnp_batch.hip", "pnp_lo.hip", "pnp_lo_batch.hip", "affine.hip", "pose_metrics.hip", "ingest.hip", "track.hip", "profile.hip", "bn_train.hip", "bankbuild.hip", "pointcloud.hip", "loss.hip", "linear_bwd.hip",
+           "coarse_match.hip", "fine.hip", "loftr2d.hip", "pnp.hip", "pnp_batch.hip", "pnp_lo.hip", "pnp_lo_batch.hip", "affine.hip", "pose_metrics.hip", "ingest.hip", "track.hip", "profile.hip", "bn_train.hip", "bankbuild.hip", "pointcloud.hip", "loss.hip", "linear_bwd.hip",
            "linattn_train.hip", "conv_bwd.hip", "train_misc.hip", "conv_tail.hip", "optim.hip", "train_sample.hip", "version.hip", "api.hip"]
 HEADERS = ["opp_common.h", "opp_internal.h", "enc_frag.h", "pnp_math.h", "pnp_sample.h", "pnp_args.h", "pnp_body.h", "pnp_batch.h", "pnp_lo_body.h", "pnp_lo_batch.h", "affine_batch.h", os.path.join("..", "..", "include", "opp_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

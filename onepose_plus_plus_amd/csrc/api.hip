@@ -272,7 +272,17 @@ extern "C" int opp_create(const opp_config* cfg, opp_ctx** out) {
   OPP_CHECK_ARG(cfg->encoder_fusion >= 0 && cfg->encoder_fusion <= 2, "encoder_fusion must be 0, 1 or 2");
   OPP_CHECK_ARG(cfg->fpn_overlap == 0 || cfg->fpn_overlap == 1, "fpn_overlap must be 0 or 1");
   OPP_CHECK_ARG(cfg->score_two_sweep >= 0 && cfg->score_two_sweep <= 2, "score_two_sweep must be 0, 1 or 2");
-  OPP_CHECK_ARG(cfg->fine_window >= 1 && cfg->fine_window * cfg->fine_window <= 64 && (cfg->fine_window & 1), "bad fine window");
+  // the 2D-2D schedule (opp_fine2d) takes windows up to 9 x 9; the 2D-3D fine entries keep one lane per cell (fine_tail_checks)
+  OPP_CHECK_ARG(cfg->fine_window >= 1 && cfg->fine_window * cfg->fine_window <= (cfg->cross_sequential ? 81 : 64) && (cfg->fine_window & 1), "bad fine window");
+  if (cfg->cross_sequential != 0 && cfg->cross_sequential != 1) {
+    opp_set_error("cross_sequential must be 0 or 1, got %d", cfg->cross_sequential);
+    return OPP_ERR_UNSUPPORTED;
+  }
+  if (cfg->cross_sequential && (cfg->encoder_fusion != 0 || cfg->coarse_attention != 0 || cfg->fine_attention != 0)) {
+    opp_set_error("cross_sequential runs with encoder_fusion 0 and linear attention (got fusion %d, attention %d / %d)", cfg->encoder_fusion,
+                  cfg->coarse_attention, cfg->fine_attention);
+    return OPP_ERR_UNSUPPORTED;
+  }
   if ((cfg->coarse_attention != 0 && cfg->coarse_attention != 1) || (cfg->fine_attention != 0 && cfg->fine_attention != 1)) {
     opp_set_error("coarse_attention / fine_attention must be 0 (linear) or 1 (full), got %d / %d", cfg->coarse_attention, cfg->fine_attention);
     return OPP_ERR_UNSUPPORTED;
@@ -1663,6 +1673,7 @@ struct TrOpts {
   int fusion;                            // opp_config.encoder_fusion: 0 dense GEMMs, 1 one 32-token kernel behind the projection, 2 64-token tiles
   int prefix_mode = OPP_PREFIX_NONE;     // OPP_PREFIX_*, with `pre` the blob to read (USE) or fill (MAKE)
   const ObjPrefix* pre = nullptr;
+  bool sequential = false;               // opp_config.cross_sequential: a cross layer updates stream 0, then stream 1 from the updated stream 0
 };
 
 // The A/B switches of the walk (tools and tests; all on by default).  OPP_FUSE_LN=0: LayerNorms of the dense tail as their own launches;
@@ -1752,12 +1763,74 @@ int transformer_checks(const EncLevel& lv, int n_seg, int len0, int len1, int h2
     OPP_CHECK_ARG(h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3, "transformer: full attention runs in fp32 or bf16x3");
     OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: full attention needs both token streams");
   }
+  if (o.sequential)
+    OPP_CHECK_ARG(!lv.full && o.fusion == 0 && o.prefix_mode == OPP_PREFIX_NONE && !o.mask0 && (h2 == OPP_PREC_FP32 || h2 == OPP_PREC_BF16X3),
+                  "transformer: the sequential cross schedule runs unfused, with linear attention, no mask and no object prefix");
+  // many segments (the fine level) run one workgroup per segment and stream or not at all: nothing sends M x (W^2 + W^2) tokens through the
+  // generic gather + apply pair
+  if (o.sequential && n_seg > 1)
+    OPP_CHECK_ARG(opp_linattn_seg_ok(len0, len1, lv.C, lv.D()), "transformer: sequential schedule over %d segments needs d_model 128 / 8 heads and at most "
+                                                                "81 tokens per stream (got %d + %d)", n_seg, len0, len1);
   if (o.prefix_mode != OPP_PREFIX_NONE)
     OPP_CHECK_ARG(o.pre && !lv.full && n_seg == 1 && lv.C == 256 && lv.D() == 32 && o.fusion == 2 && h2 == OPP_PREC_BF16X3 && lv.layers.size() >= 2 &&
                       !lv.is_cross[0] && lv.is_cross[1] && (o.prefix_mode == OPP_PREFIX_USE || len0 == 0),
                   "transformer: object prefix on an unsupported configuration");
   return OPP_OK;
 }
+// ---- the sequential schedule of the 2D-2D matcher (opp_config.cross_sequential) ------------------------------------------------------
+// rows [row0, row0 + rows) x columns [col0, col0 + ncols) of one layer's q | k | v projection into the same columns of dst [.][3 C]: phi on the
+// q / k columns, v / S on the v columns, S = `seg_len`, the length of the stream the rows belong to (transformer.py:76-79, linear_attention.py:49-53)
+OppGemm qkv_part_gemm(const EncLayerDesc& e, const float* X, int C, int row0, int rows, int col0, int ncols, int seg_len, float* dst, int h2) {
+  OppGemm g;
+  g.nonfinite = t_status_flag;
+  g.tile_policy = t_tile_policy;
+  g.A0 = X + (size_t)row0 * C;
+  g.lda0 = C;
+  g.ksplit = C;
+  g.ldw = (int)split_floats((size_t)C, h2);
+  g.W = e.wqkv + (size_t)col0 * g.ldw;
+  g.M = rows;
+  g.N = ncols;
+  g.K = C;
+  g.C = dst + (size_t)row0 * 3 * C + col0;
+  g.ldc = 3 * C;
+  g.n_store = ncols;
+  g.prec = h2;
+  g.act = OPP_ACT_QKV;
+  g.qk_cols = 2 * C - col0 > 0 ? 2 * C - col0 : 0;
+  g.split_row = 0;
+  g.s0 = g.s1 = (float)seg_len;
+  g.h2_inv = nullptr;
+  return g;
+}
+// LinearAttention of ONE stream (phi(Q) rows at q) against the phi(K) | V / S columns of a source stream (rows at src), both inside a
+// [.][3 C] projection buffer: short segments in one workgroup each (loftr2d.hip), else the generic gather + apply
+int run_linattn_one(const float* q, const float* src, int C, int D, int n_seg, int len_q, int len_src, const AttnBufs& b, float* msg, float eps,
+                    hipStream_t s) {
+  if (opp_linattn_seg_ok(len_q, len_src, C, D)) return opp_linattn_seg(q, src + C, src + 2 * C, 3 * C, n_seg, len_q, len_src, msg, C, C, D, eps, s);
+  OPP_TRY(opp_linattn_kv(src + C, src + 2 * C, 3 * C, n_seg, len_src, C, D, b.kv, b.ks, b.scratch, s));
+  return opp_linattn_apply(q, 3 * C, b.kv, b.ks, msg, C, n_seg, len_q, len_src, C, D, eps, s);
+}
+// one layer of the sequential schedule, in place on X = [stream 0 ; stream 1].  self: f0 = layer(f0, f0), f1 = layer(f1, f1); cross:
+// f0 = layer(f0, f1), then f1 = layer(f1, f0) with the UPDATED f0.  Every stream's q, k, v are projected once: everything but stream 0's
+// k | v of a cross layer in front, those two behind stream 0's update.  The message and the dense tail use the head of the buffers per stream.
+int sequential_layer(const EncLevel& lv, const EncLayerDesc& e, bool cross, float* X, int n_seg, int len0, int len1, const TrBufs& b, bool fuse_ln,
+                     hipStream_t s, int h2) {
+  const int C = lv.C, D = lv.D();
+  const int T0 = n_seg * len0, T1 = n_seg * len1;
+  const float eps_attn = 1e-6f, eps_ln = 1e-5f;
+  float* X1 = X + (size_t)T0 * C;
+  const float* p0 = b.qkv;
+  const float* p1 = b.qkv + (size_t)T0 * 3 * C;
+  OPP_TRY(opp_gemm_launch(qkv_part_gemm(e, X, C, 0, T0, 0, cross ? C : 3 * C, len0, b.qkv, h2), s));
+  OPP_TRY(opp_gemm_launch(qkv_part_gemm(e, X, C, T0, T1, 0, 3 * C, len1, b.qkv, h2), s));
+  OPP_TRY(run_linattn_one(p0, cross ? p1 : p0, C, D, n_seg, len0, cross ? len1 : len0, b, b.msg, eps_attn, s));
+  OPP_TRY(encoder_tail_dense(e, X, b, T0, C, fuse_ln, eps_ln, s, h2));
+  if (cross) OPP_TRY(opp_gemm_launch(qkv_part_gemm(e, X, C, 0, T0, C, 2 * C, len0, b.qkv, h2), s));
+  OPP_TRY(run_linattn_one(p1, cross ? p0 : p1, C, D, n_seg, len1, cross ? len0 : len1, b, b.msg, eps_attn, s));
+  return encoder_tail_dense(e, X1, b, T1, C, fuse_ln, eps_ln, s, h2);
+}
+
 int transformer_impl(const EncLevel& lv, float* X, int n_seg, int len0, int len1, const TrBufs& b, hipStream_t s, int h2, const TrOpts& o) {
   const std::vector<EncLayerDesc>& layers = lv.layers;
   const int C = lv.C, D = lv.D();
@@ -1776,6 +1849,11 @@ int transformer_impl(const EncLevel& lv, float* X, int n_seg, int len0, int len1
   // ... and reduces its tile's phi(K)^T V, sum phi(K) for layer li + 1.  The object-prefix builder keeps the gather: its projection rows
   // are part of the prefix blob
   const bool kv_fold = sw.kv_fold && qkv_fold && o.prefix_mode != OPP_PREFIX_MAKE;
+  if (o.sequential) {
+    OPP_CHECK_ARG(len0 > 0 && len1 > 0, "transformer: the sequential schedule needs both token streams");
+    for (size_t li = 0; li < layers.size(); ++li) OPP_TRY(sequential_layer(lv, layers[li], lv.is_cross[li] != 0, X, n_seg, len0, len1, b, fuse_ln, s, h2));
+    return OPP_OK;
+  }
   bool kv_parts = false;      // the previous layer's kernel left this layer's KV / Ksum chunk partials in b.scratch
   for (size_t li = 0; li < layers.size(); ++li) {
     const EncLayerDesc& e = layers[li];
@@ -1971,7 +2049,8 @@ extern "C" int opp_transformer(opp_ctx* ctx, int which, float* tokens, int n_seg
     OPP_CHECK_ARG(n_seg != 1 || !ctx->query_mask, "transformer: full attention with a query mask is unsupported (upstream FullAttention indexes the "
                                                   "None q_mask of the cross layers, linear_attention.py:84-85)");
   if (transformer_is_noop(lv, n_seg, len0, len1)) return OPP_OK;
-  const TrOpts opts = {.mask0 = which == 0 && n_seg == 1 ? ctx->query_mask : nullptr, .fusion = ctx->cfg.encoder_fusion};
+  const TrOpts opts = {.mask0 = which == 0 && n_seg == 1 ? ctx->query_mask : nullptr, .fusion = ctx->cfg.encoder_fusion,
+                       .sequential = ctx->cfg.cross_sequential != 0};
   OPP_TRY(transformer_checks(lv, n_seg, len0, len1, gemm_prec(ctx->cfg), opts));
   Arena a(ws, ws_bytes);
   TrBufs b;
@@ -2004,6 +2083,54 @@ size_t plan_coarse_match(const opp_ctx* c, int n, int L, Arena& a, MatchBufs& b)
   return a.peak;
 }
 
+// The materialised score path, shared by the 2D-3D matcher and opp_match2d: conf [n][L] = (rows . cols) * out_mul / out_div on the MFMA GEMM with the
+// dual-softmax (max, sum exp) partials fused into its epilogue, then the in-place confidences and the selection (two_d: the 2D-2D one).  The
+// partial layout and the tile rows the selection merges by are chosen HERE, in one place.  cols_split: scratch for the pre-split column operand
+// when sprec is a split arithmetic.  C = 256: the 1/16 feature scaling is an exact power of two, so it commutes with the sum.
+int score_gemm_select(opp_ctx* c, const float* rows, const float* cols, int n, int L, int wc, float out_mul, float out_div, const float* col_mask,
+                      int sprec, float* cols_split, float* stats, float* scratch, const float* kpts, float base_scale, const float* qscale, float* conf,
+                      long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c, float* mkpts_3d, int* count, const OppSelect2D* two_d,
+                      hipStream_t s) {
+  const int C = c->cfg.coarse_d_model;
+  OppGemm g;
+  g.nonfinite = t_status_flag;
+  g.tile_policy = t_tile_policy;
+  g.A0 = rows;
+  g.lda0 = C;
+  g.ksplit = C;
+  g.W = cols;
+  g.ldw = C;
+  g.M = n;
+  g.N = L;
+  g.K = C;
+  g.C = conf;
+  g.ldc = L;
+  g.n_store = L;
+  g.out_mul = out_mul;
+  g.out_div = out_div;
+  g.col_mask = col_mask;           // masked image cells get -1e9 (coarse_matching.py:108-114), or null
+  // tile rows of the score GEMM: 128 (config 0 / 25); bf16x3 with enough rows: the 256x128 8-wave tile (config 20)
+  const int score_cfg = sprec == OPP_PREC_BF16X3 ? (n >= 512 ? 20 : 25) : 0;
+  const int score_bm = score_cfg == 20 ? 256 : 128;
+  {  // dual-softmax (max, sum exp) partials fused into the epilogue: [n][tn] x2, [tm][L] x2
+    const size_t tn = opp_cdiv(L, 128), tm = opp_cdiv(n, score_bm);
+    g.stat_rowmax = stats;
+    g.stat_rowsum = g.stat_rowmax + (size_t)n * tn;
+    g.stat_colmax = g.stat_rowsum + (size_t)n * tn;
+    g.stat_colsum = g.stat_colmax + tm * (size_t)L;
+  }
+  if (sprec != OPP_PREC_FP32) {   // the column tokens are the "weight" operand here: split them once per image (4 / 6 MB), unscaled
+    if (sprec == OPP_PREC_BF16X3) OPP_TRY(opp_b3_split(cols, cols_split, (size_t)L * C, s));
+    else OPP_TRY(opp_h2_split(cols, cols_split, (size_t)L * C, nullptr, s));
+    g.W = cols_split;
+    g.ldw = (int)split_floats((size_t)C, sprec);
+    g.prec = sprec;
+  }
+  OPP_TRY(opp_gemm_launch_cfg(g, score_cfg, s));   // the partial layout above assumes this tile shape
+  return opp_dual_softmax_select(conf, n, L, wc, c->cfg.match_thr, c->cfg.match_border_rm, kpts, base_scale, qscale, stats, score_bm, scratch, i_ids, j_ids,
+                                 mconf, mkpts_c, mkpts_3d, count, s, two_d);
+}
+
 int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int hc, int wc, const float* kpts, float base_scale,
                       const float* qscale, float* conf, long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c,
                       float* mkpts_3d, int* count, const MatchBufs& mb, hipStream_t s) {
@@ -2032,44 +2159,8 @@ int coarse_match_impl(opp_ctx* c, const float* f3, const float* f2, int n, int h
                                       i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, s);
   }
   // sim = (f3/sqrt(C)) . (f2/sqrt(C)) / (temperature + 1e-4)   (coarse_matching.py:99-107).
-  // C = 256: the 1/16 feature scaling is an exact power of two, so it commutes with the sum.
-  OppGemm g;
-  g.nonfinite = t_status_flag;
-  g.tile_policy = t_tile_policy;
-  g.A0 = f3;
-  g.lda0 = C;
-  g.ksplit = C;
-  g.W = f2;
-  g.ldw = C;
-  g.M = n;
-  g.N = L;
-  g.K = C;
-  g.C = conf;
-  g.ldc = L;
-  g.n_store = L;
-  g.out_mul = feat_mul;
-  g.out_div = (float)((double)c->cfg.match_temperature + 1e-4);
-  g.col_mask = c->query_mask;      // masked image cells get -1e9 (coarse_matching.py:108-114), or null
-  // tile rows of the score GEMM: 128 (config 0 / 25); bf16x3 with enough rows: the 256x128 8-wave tile (config 20)
-  const int score_cfg = sprec == OPP_PREC_BF16X3 ? (n >= 512 ? 20 : 25) : 0;
-  const int score_bm = score_cfg == 20 ? 256 : 128;
-  {  // dual-softmax (max, sum exp) partials fused into the epilogue: [n][tn] x2, [tm][L] x2
-    const size_t tn = opp_cdiv(L, 128), tm = opp_cdiv(n, score_bm);
-    g.stat_rowmax = stats;
-    g.stat_rowsum = g.stat_rowmax + (size_t)n * tn;
-    g.stat_colmax = g.stat_rowsum + (size_t)n * tn;
-    g.stat_colsum = g.stat_colmax + tm * (size_t)L;
-  }
-  if (sprec != OPP_PREC_FP32) {   // the image tokens are the "weight" operand here: split them once per image (4 / 6 MB), unscaled
-    if (sprec == OPP_PREC_BF16X3) OPP_TRY(opp_b3_split(f2, f2_split, (size_t)L * C, s));
-    else OPP_TRY(opp_h2_split(f2, f2_split, (size_t)L * C, nullptr, s));
-    g.W = f2_split;
-    g.ldw = (int)split_floats((size_t)C, sprec);
-    g.prec = sprec;
-  }
-  OPP_TRY(opp_gemm_launch_cfg(g, score_cfg, s));   // the partial layout above assumes this tile shape
-  return opp_dual_softmax_select(conf, n, L, wc, c->cfg.match_thr, c->cfg.match_border_rm, kpts, base_scale, qscale, stats, score_bm, scratch, i_ids, j_ids,
-                                 mconf, mkpts_c, mkpts_3d, count, s);
+  return score_gemm_select(c, f3, f2, n, L, wc, feat_mul, (float)((double)c->cfg.match_temperature + 1e-4), c->query_mask, sprec, f2_split, stats, scratch,
+                           kpts, base_scale, qscale, conf, i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count, nullptr, s);
 }
 
 }  // namespace
@@ -2187,6 +2278,8 @@ extern "C" int opp_forward_coarse(opp_ctx* ctx, const float* image, int H, int W
   OPP_CHECK_ARG(ctx && ctx->packed && image && kpts && (bank_c || tokens3d_pre) && conf && ws, "forward_coarse: null argument");
   OPP_CHECK_ARG(ctx->tr_packed, "forward_coarse: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
   OPP_CHECK_ARG(n > 0, "forward_coarse: empty point cloud");
+  OPP_CHECK_ARG(!ctx->cfg.cross_sequential, "forward_coarse: a 2D-2D context (cross_sequential) has no 2D-3D forward; its stages are opp_backbone, "
+                                            "opp_image_tokens, opp_transformer, opp_match2d and opp_fine2d");
   OPP_CHECK_ARG(!ctx->cfg.pos_enc_enable || pe, "forward_coarse: positional encoding enabled but pe is null");
   OPP_CHECK_ARG(!ctx->cfg.coarse_attention || !ctx->query_mask, "forward_coarse: full attention with a query mask is unsupported (upstream "
                                                                 "FullAttention indexes the None q_mask of the cross layers, linear_attention.py:84-85)");
@@ -2251,6 +2344,8 @@ size_t plan_fine_tail(const opp_ctx* c, int M, Arena& a, TrBufs& tr) {
 }
 // the argument checks of fine_tail's transformer (asked before the plan, as in every entry that runs one)
 int fine_tail_checks(const opp_ctx* c, int M, int run_transformer) {
+  OPP_CHECK_ARG(c->cfg.fine_window * c->cfg.fine_window <= 64 && !c->cfg.cross_sequential,
+                "fine: a 2D-2D context (cross_sequential, windows up to 9 x 9) runs its fine level through opp_fine2d");
   if (!run_transformer) return OPP_OK;
   return transformer_checks(level_of(c, 1), M, c->cfg.fine_window * c->cfg.fine_window, 1, gemm_prec(c->cfg), {.fusion = c->cfg.encoder_fusion});
 }
@@ -2403,6 +2498,114 @@ extern "C" int opp_fine(opp_ctx* ctx, const float* feat_f, int Hf, int Wf, const
   OppProfScope prof(OPP_PROF_FINE, s, (double)M * ((double)(WW + 1) * C * 4.0 + 5 * 4.0));
   OPP_TRY(opp_fine_gather(feat_f, Hf, Wf, C, bank_f, n, i_ids, j_ids, M, wc, Hf / hc, Wwin, C, X, C, f3, C, s));
   return fine_tail(ctx, X, M, mkpts_c, base_scale, qscale, run_transformer, expec_f, mkpts_f, b.tr, s);
+}
+
+// ----------------------------------------------------------------------------------------
+// 2D-2D matching (LoFTR): image tokens, coarse matching of two images, fine level on two windows per match
+// ----------------------------------------------------------------------------------------
+namespace {
+// opp_match2d: selection scratch, statistics partials of the score GEMM, image 1's tokens pre-split when the score GEMM runs on split operands
+struct Match2dBufs {
+  float *scratch = nullptr, *stats = nullptr, *f1_split = nullptr;
+  int sprec = OPP_PREC_FP32;
+};
+size_t plan_match2d(const opp_ctx* c, int L0, int L1, Arena& a, Match2dBufs& b) {
+  const int C = c->cfg.coarse_d_model;
+  b.scratch = a.f(opp_coarse_match_scratch_floats(L0, L1));
+  b.stats = a.f(opp_coarse_match_stats_floats(L0, L1));
+  b.sprec = score_prec(c->cfg);
+  b.f1_split = b.sprec != OPP_PREC_FP32 ? a.f(split_floats((size_t)L1 * C, b.sprec)) : nullptr;
+  return a.peak;
+}
+// opp_fine2d: [M * WW window tokens of image 0 ; M * WW of image 1], then the transformer's buffers
+struct Fine2dBufs {
+  float* X;
+  TrBufs tr;
+};
+size_t plan_fine2d(const opp_ctx* c, int M, Arena& a, Fine2dBufs& b) {
+  const int WW = c->cfg.fine_window * c->cfg.fine_window;
+  const EncLevel lv = level_of(c, 1);
+  b.X = a.f((size_t)2 * M * WW * lv.C);
+  return plan_transformer(lv.C, lv.D(), M, WW, WW, a, b.tr);
+}
+}  // namespace
+
+extern "C" int opp_image_tokens(opp_ctx* ctx, const float* feat_c, const float* pe, int L, float* tokens, void* stream) {
+  OPP_CHECK_ARG(ctx && feat_c && tokens && L > 0, "image_tokens: bad argument");
+  const size_t n = (size_t)L * ctx->cfg.coarse_d_model;
+  if (pe) return opp_add(feat_c, pe, tokens, n, (hipStream_t)stream);
+  if (hipMemcpyAsync(tokens, feat_c, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess) {
+    opp_set_error("image_tokens: copy failed");
+    return OPP_ERR_LAUNCH;
+  }
+  return OPP_OK;
+}
+
+extern "C" size_t opp_match2d_workspace_bytes(const opp_ctx* ctx, int L0, int L1) {
+  if (!ctx || L0 <= 0 || L1 <= 0) return 0;
+  Arena a(nullptr, 0);
+  Match2dBufs b;
+  return opp_align(plan_match2d(ctx, L0, L1, a, b)) + 256;
+}
+
+extern "C" int opp_match2d(opp_ctx* ctx, const float* f0, const float* f1, int h0c, int w0c, int h1c, int w1c, float base_scale, const float* scale0,
+                           const float* scale1, float* conf, long long* i_ids, long long* j_ids, float* mconf, float* mkpts0_c, float* mkpts1_c,
+                           int* count, void* ws, size_t ws_bytes, void* stream) {
+  FlagScope flag_scope(ctx);
+  OPP_CHECK_ARG(ctx && f0 && f1 && conf && i_ids && j_ids && mconf && mkpts0_c && mkpts1_c && count && ws, "match2d: null argument");
+  OPP_CHECK_ARG(h0c > 0 && w0c > 0 && h1c > 0 && w1c > 0 && (size_t)h0c * w0c * h1c * w1c < (1ull << 31), "match2d: bad grid %d x %d / %d x %d", h0c, w0c,
+                h1c, w1c);
+  OPP_CHECK_ARG(ctx->cfg.match_border_rm >= 0, "match2d: negative border");
+  hipStream_t s = (hipStream_t)stream;
+  const int C = ctx->cfg.coarse_d_model, L0 = h0c * w0c, L1 = h1c * w1c;
+  Arena a(ws, ws_bytes);
+  Match2dBufs b;
+  plan_match2d(ctx, L0, L1, a, b);
+  OPP_CHECK_WS(a.ok, "match2d: workspace too small");
+  OppSelect2D two_d;
+  two_d.h0 = h0c;
+  two_d.w0 = w0c;
+  two_d.scale0 = scale0;
+  two_d.mkpts0 = mkpts0_c;
+  // sim = (f0 / sqrt(C)) . (f1 / sqrt(C)) / temperature, exactly as configured: image 0's cells are the rows, image 1's the columns
+  return score_gemm_select(ctx, f0, f1, L0, L1, w1c, 1.0f / (float)C, ctx->cfg.match_temperature, nullptr, b.sprec, b.f1_split, b.stats, b.scratch, nullptr,
+                           base_scale, scale1, conf, i_ids, j_ids, mconf, mkpts1_c, nullptr, count, &two_d, s);
+}
+
+extern "C" size_t opp_fine2d_workspace_bytes(const opp_ctx* ctx, int M) {
+  if (!ctx || M <= 0) return 256;
+  Arena a(nullptr, 0);
+  Fine2dBufs b;
+  return opp_align(plan_fine2d(ctx, M, a, b)) + 256;
+}
+
+extern "C" int opp_fine2d(opp_ctx* ctx, const float* feat_f0, int Hf0, int Wf0, const float* feat_f1, int Hf1, int Wf1, const long long* i_ids,
+                          const long long* j_ids, int M, int w0c, int w1c, int stride, const float* mkpts1_c, float base_scale, const float* scale1,
+                          float* expec_f, float* mkpts1_f, void* ws, size_t ws_bytes, void* stream) {
+  FlagScope flag_scope(ctx);
+  if (M <= 0) return OPP_OK;
+  OPP_CHECK_ARG(ctx && ctx->packed && feat_f0 && feat_f1 && i_ids && j_ids && mkpts1_c && expec_f && mkpts1_f && ws, "fine2d: null argument");
+  OPP_CHECK_ARG(ctx->tr_packed, "fine2d: weights were packed with scope 1 (backbone only); repack with opp_set_pack_scope(ctx, 0)");
+  OPP_CHECK_ARG(Hf0 > 0 && Wf0 > 0 && Hf1 > 0 && Wf1 > 0 && w0c > 0 && w1c > 0 && stride > 0 && Wf0 == w0c * stride && Wf1 == w1c * stride &&
+                    Hf0 % stride == 0 && Hf1 % stride == 0,
+                "fine2d: fine maps %d x %d / %d x %d are not whole coarse grids of widths %d / %d at stride %d", Hf0, Wf0, Hf1, Wf1, w0c, w1c, stride);
+  hipStream_t s = (hipStream_t)stream;
+  const EncLevel lv = level_of(ctx, 1);
+  const int C = lv.C, Wwin = ctx->cfg.fine_window, WW = Wwin * Wwin;
+  OPP_CHECK_ARG(Wwin >= 3, "fine2d: window %d (odd, 3 .. 9)", Wwin);
+  const TrOpts opts = {.fusion = ctx->cfg.encoder_fusion, .sequential = ctx->cfg.cross_sequential != 0};
+  OPP_TRY(transformer_checks(lv, M, WW, WW, gemm_prec(ctx->cfg), opts));
+  Arena a(ws, ws_bytes);
+  Fine2dBufs b;
+  plan_fine2d(ctx, M, a, b);
+  OPP_CHECK_WS(a.ok, "fine2d: workspace too small");
+  float* const X = b.X;
+  OPP_TRY(opp_window_gather2(feat_f0, Hf0, Wf0, feat_f1, Hf1, Wf1, i_ids, j_ids, M, w0c, w1c, stride, Wwin, C, X, s));
+  OPP_TRY(transformer_impl(lv, X, M, WW, WW, b.tr, s, gemm_prec(ctx->cfg), opts));
+  // FineMatching with the centre token of window 0 as the query (LoFTR fine_matching: feat_f0[:, WW / 2]); 1 / sqrt(C) as fine_matching.py:82
+  const float temp = (float)(1.0 / sqrt((double)C));
+  return opp_fine_head_wide(X + (size_t)(WW / 2) * C, (size_t)WW * C, X + (size_t)M * WW * C, C, M, Wwin, C, temp, mkpts1_c, base_scale, scale1, expec_f,
+                            mkpts1_f, s);
 }
 
 // ----------------------------------------------------------------------------------------

@@ -451,6 +451,77 @@ __global__ __launch_bounds__(1024) void select_kernel(const float* __restrict__ 
   if (tid == 0) *count = running;
 }
 
+// The same selection for two images (LoFTR's CoarseMatching; rows = cells of image 0's h0 x w0 grid, columns = cells of image 1's h1 x w1
+// grid): mask_border clears `border` cells at BOTH ends of both grids, and both images' keypoints are emitted.
+__global__ __launch_bounds__(1024) void select2d_kernel(const float* __restrict__ conf, int N, int L, int h0, int w0, int h1, int w1,
+                                                        const float* __restrict__ row_cmax, const int* __restrict__ row_arg,
+                                                        const int* __restrict__ row_ties, const float* __restrict__ col_cmax, float thr, int border,
+                                                        float base_scale, const float* __restrict__ scale0, const float* __restrict__ scale1,
+                                                        long long* __restrict__ i_ids, long long* __restrict__ j_ids, float* __restrict__ mconf,
+                                                        float* __restrict__ mkpts0, float* __restrict__ mkpts1, int* __restrict__ count) {
+  __shared__ int wave_tot[16];
+  __shared__ int running;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) running = 0;
+  const float sx0 = scale0 ? base_scale * scale0[1] : base_scale, sy0 = scale0 ? base_scale * scale0[0] : base_scale;
+  const float sx1 = scale1 ? base_scale * scale1[1] : base_scale, sy1 = scale1 ? base_scale * scale1[0] : base_scale;
+  auto inside = [border](int y, int x, int h, int w) { return y >= border && y < h - border && x >= border && x < w - border; };
+  __syncthreads();
+  for (int base = 0; base < N; base += 1024) {
+    const int i = base + tid;
+    const int iy = i / w0, ix = i - iy * w0;
+    int sel = -1;
+    float c = 0.f;
+    if (i < N) {
+      c = row_cmax[i];
+      if (c > thr && inside(iy, ix, h0, w0)) {
+        if (row_ties[i] == 1) {
+          const int j = row_arg[i];
+          const int jy = j / w1, jx = j - jy * w1;
+          if (inside(jy, jx, h1, w1) && c == col_cmax[j]) sel = j;
+        } else {  // exact ties inside the row (rare): first column that survives every test
+          const float* r = conf + (size_t)i * L;
+          for (int j = 0; j < L; ++j) {
+            if (r[j] == c && c == col_cmax[j]) {
+              const int jy = j / w1, jx = j - jy * w1;
+              if (inside(jy, jx, h1, w1)) {
+                sel = j;
+                break;
+              }
+            }
+          }
+        }
+      }
+    }
+    const int flag = sel >= 0 ? 1 : 0;
+    const unsigned long long bal = __ballot(flag);
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(bal);
+    __syncthreads();
+    int off = running;
+    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    if (flag) {
+      const int m = off + before;
+      i_ids[m] = i;
+      j_ids[m] = sel;
+      mconf[m] = c;
+      const int jy = sel / w1, jx = sel - jy * w1;
+      mkpts0[2 * m + 0] = (float)ix * sx0;
+      mkpts0[2 * m + 1] = (float)iy * sy0;
+      mkpts1[2 * m + 0] = (float)jx * sx1;
+      mkpts1[2 * m + 1] = (float)jy * sy1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int tot = 0;
+      for (int w = 0; w < 16; ++w) tot += wave_tot[w];
+      running += tot;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) *count = running;
+}
+
 // merges of the per-tile partials of the confidence sweep (gemm_ss.hip, OPP_SS_CONF; cells = GEMM rows, points = columns)
 // per point: best = max over the cell tiles, arg = the first cell holding it (tiles are in ascending cell order and each
 // partial is its tile's first such cell), ties = how many cells hold it.  Partials [T][N], thread per point.
@@ -504,8 +575,10 @@ size_t opp_coarse_match_scratch_floats(int N, int L) {
 // S (in: similarity, out: confidence matrix) [N][L].  Outputs have capacity N.
 int opp_dual_softmax_select(float* S, int N, int L, int wc, float thr, int border, const float* kpts, float base_scale,
                             const float* qscale, const float* stats, int stats_bm, float* scratch, long long* i_ids, long long* j_ids, float* mconf, float* mkpts_c,
-                            float* mkpts_3d, int* count, hipStream_t stream) {
+                            float* mkpts_3d, int* count, hipStream_t stream, const OppSelect2D* two_d) {
   OPP_CHECK_ARG(N > 0 && L > 0 && wc > 0 && L % wc == 0, "coarse match: bad sizes N=%d L=%d wc=%d", N, L, wc);
+  OPP_CHECK_ARG(!two_d || (two_d->mkpts0 && two_d->w0 > 0 && two_d->h0 * two_d->w0 == N), "coarse match: image 0's grid %d x %d is not the %d rows",
+                two_d ? two_d->h0 : 0, two_d ? two_d->w0 : 0, N);
   OPP_CHECK_ARG(!stats || stats_bm == 128 || stats_bm == 256 || stats_bm == -1, "coarse match: statistics come from 128- or 256-row GEMM tiles");
   const int chunks = opp_cdiv(N, 128);
   const size_t Np = (size_t)opp_cdiv(N, 4) * 4, Lp = (size_t)opp_cdiv(L, 4) * 4;
@@ -547,6 +620,11 @@ int opp_dual_softmax_select(float* S, int N, int L, int wc, float thr, int borde
   const size_t conf_lds = fuse_cmax ? (size_t)L * 4 : 0;
   float* cpart = fuse_cmax ? part : nullptr;
   auto select = [&]() {
+    if (two_d) {
+      hipLaunchKernelGGL(select2d_kernel, dim3(1), dim3(1024), 0, stream, S, N, L, two_d->h0, two_d->w0, L / wc, wc, row_cmax, row_arg, row_ties, col_cmax,
+                         thr, border, base_scale, two_d->scale0, qscale, i_ids, j_ids, mconf, two_d->mkpts0, mkpts_c, count);
+      return;
+    }
     hipLaunchKernelGGL(select_kernel, dim3(1), dim3(1024), 0, stream, S, N, L, wc, row_cmax, row_arg, row_ties, col_cmax, thr,
                        border, kpts, base_scale, qscale, i_ids, j_ids, mconf, mkpts_c, mkpts_3d, count);
   };

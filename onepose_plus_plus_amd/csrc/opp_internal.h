@@ -266,9 +266,25 @@ int opp_dual_softmax_ss_single(const void* f3s, const void* f2s, int C, int N, i
                                const float* col_mask, float thr, int border, const float* kpts, float base_scale, const float* qscale,
                                float* conf, float* stats, float* scratch, long long* i_ids, long long* j_ids, float* mconf,
                                float* mkpts_c, float* mkpts_3d, int* count, hipStream_t stream);
+// two_d != null: the selection of the 2D-2D matcher (rows = the cells of image 0's h0 x w0 grid, columns = image 1's L / wc x wc grid): the
+// border is cleared at both ends of both grids, mkpts_c receives image 1's keypoints and two_d->mkpts0 image 0's; kpts / mkpts_3d are unused
+struct OppSelect2D {
+  int h0 = 0, w0 = 0;
+  const float* scale0 = nullptr;     // (h_scale, w_scale) of image 0 on the device, or null
+  float* mkpts0 = nullptr;           // [capacity N][2]
+};
 int opp_dual_softmax_select(float* S, int N, int L, int wc, float thr, int border, const float* kpts,
                             float base_scale, const float* qscale, const float* stats, int stats_bm, float* scratch, long long* i_ids, long long* j_ids, float* mconf,
-                            float* mkpts_c, float* mkpts_3d, int* count, hipStream_t stream);
+                            float* mkpts_c, float* mkpts_3d, int* count, hipStream_t stream, const OppSelect2D* two_d = nullptr);
+// loftr2d.hip -- the 2D-2D matcher's own kernels: windows of two fine maps, per-segment linear attention of one stream against a source
+// stream (<= 81 tokens each, C = 128, D = 16), the expectation head for windows of more than 64 cells
+int opp_window_gather2(const float* feat0, int Hf0, int Wf0, const float* feat1, int Hf1, int Wf1, const long long* i_ids, const long long* j_ids, int M,
+                       int w0c, int w1c, int stride, int Wwin, int C, float* win, hipStream_t stream);
+bool opp_linattn_seg_ok(int len_q, int len_src, int C, int D);
+int opp_linattn_seg(const float* q, const float* k, const float* v, int ld, int n_seg, int len_q, int len_src, float* out, int ldo, int C, int D, float eps,
+                    hipStream_t stream);
+int opp_fine_head_wide(const float* f3, size_t ld3, const float* win, int ldw, int M, int Wwin, int C, float temp, const float* mkpts_c, float base_scale,
+                       const float* qscale, float* expec, float* mkpts_f, hipStream_t stream);
 // fine.hip
 int opp_fine_patch_gather(const float* x1, int Hf, int Wf, int c1, const float* x2o, int c2, const long long* j_ids, int M, int wc, int stride, int org, int P,
                           float* xa, float* up, hipStream_t stream);
